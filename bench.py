@@ -20,13 +20,24 @@ pass, overlapped with the interior pass.  A step count that is not a multiple
 of T ends with one shorter pass, so exactly K steps are timed.
 
 Self-check: fields start from a deterministic hash of the *global* cell index
-(``utils/synthetic.py``), so every decomposition starts from the same state and
-must end in the same state; the JSON carries the all-reduced field energy
-(sum of E^2 + eta0^2 H^2 over owned cells, fp64) before and after, which
-``tests/test_bench_cpu.py`` checks against the serial run.  With
-``--fp64-companion`` (default on one GPU) the same measurement is repeated in
-fp64 -- the reference's default value type (``CMakeLists.txt:11``) -- and
-reported under ``"fp64"`` without changing the headline fields.
+(``utils/synthetic.py``), so the inputs are the same from run to run, every
+decomposition starts from the same state and must end in the same state; the
+JSON carries the all-reduced field energy (sum of E^2 + eta0^2 H^2 over owned
+cells, fp64) before and after, which ``tests/test_bench_cpu.py`` checks
+against the serial run.  (Two reductions over the fields, tens of ms each; the
+one before the warm-up also keeps the device busy up to the first step:
+without it the timed steps measured 0.3-0.9% slower.)  ``--dump-outputs DIR``
+writes what the timed path computed in its last step -- the six field
+components a caller reads through ``YeeScheme.owned_field`` -- as
+``DIR/<component>.npy`` (whole arrays of small grids, else the cells of a
+fixed hashed sample, the same cells for every component and every run;
+``dump_outputs`` below).
+
+A plain run stops there.  ``--full`` adds the companions
+(``--fp64-companion`` / ``--physics-companion``, automatic on one GPU): the
+same measurement repeated in fp64 -- the reference's default value type
+(``CMakeLists.txt:11``) -- reported under ``"fp64"``, and the BASELINE physics
+configs under ``"physics"``, without changing the headline fields.
 """
 
 from __future__ import annotations
@@ -43,6 +54,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 HEADLINE_SIZE = (1024, 1024, 1024)
 # rank grids of the headline grid measured fastest per GPU (profiles/decomp_r6.md)
 MEASURED_GRIDS = {2: (2, 1, 1), 4: (2, 2, 1), 8: (4, 2, 1)}
+# --dump-outputs: bytes written at most (all components together) and the sample's seed
+DUMP_BYTES = 48 << 20
+DUMP_SEED = 20240229
 
 
 def metric_name(size) -> str:
@@ -76,9 +90,35 @@ def parse_topology(spec: str, size, world: int, blocked: bool):
     return ParallelGridCore.create(size, world, spec)
 
 
-def run_one(a, dtype_name: str, world: int, rank: int, device: str, backend: str, core):
+def dump_outputs(scheme, out_dir: str) -> None:
+    """Write every field component's owned cells to ``out_dir/<name>.npy`` in
+    the run's own precision.  Grids whose components exceed ``DUMP_BYTES``
+    together are sampled: the cells whose linear index (x slowest) is
+    ``hash(n + DUMP_SEED) mod cells`` for n = 0, 1, ..., in that order, the
+    same cells for every component."""
+    import numpy as np
+    import torch
+    from fdtd3d_amd.utils.synthetic import _mix
+
+    os.makedirs(out_dir, exist_ok=True)
+    fields = [(c if scheme.planes == 1 else "%s_%d" % (c, p), scheme.owned_field(c, p))
+              for p in range(scheme.planes) for c in scheme.comps]
+    nx, ny, nz = fields[0][1].shape
+    cells = nx * ny * nz
+    n = DUMP_BYTES // (len(fields) * fields[0][1].element_size())
+    idx = None
+    if cells > n:
+        h = _mix(torch.arange(n, dtype=torch.int64) + DUMP_SEED)
+        lin = (((h >> 1) & ((1 << 62) - 1)) % cells).to(fields[0][1].device)
+        idx = (lin // (ny * nz), (lin // nz) % ny, lin % nz)
+    for name, f in fields:
+        v = f if idx is None else f[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), v.detach().cpu().contiguous().numpy())
+
+
+def run_one(a, dtype_name: str, world: int, rank: int, device: str, backend: str, core, dump_dir=None):
     """Build, warm up, time ``a.steps`` steps; returns a result dict (only
-    rank 0's is used)."""
+    rank 0's is used).  ``dump_dir``: write the final fields there."""
     import torch
     import torch.distributed as dist
 
@@ -199,6 +239,8 @@ def run_one(a, dtype_name: str, world: int, rank: int, device: str, backend: str
     else:
         halo_max = halo_mean = 0.0
     energy = allsum(scheme.field_energy())
+    if dump_dir:
+        dump_outputs(scheme, dump_dir)
     cells = size[0] * size[1] * size[2]
     res = {
         "mcells": cells * a.steps / dt / 1e6,
@@ -311,11 +353,17 @@ def main(argv=None) -> int:
     ap.add_argument("--init", default="random", choices=("random", "zero"),
                     help="initial fields: hash of the global cell index (random) or zero")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the field components to DIR/<name>.npy (a fixed sample of "
+                         "large grids); single-rank runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the fp64 and physics companions (--fp64-companion, --physics-companion)")
     ap.add_argument("--fp64-companion", default="auto", choices=("auto", "on", "off"),
-                    help="repeat the measurement in fp64 and report it under 'fp64' (auto: one GPU, fp32 runs)")
+                    help="with --full: repeat the measurement in fp64 and report it under 'fp64' (auto: one GPU, "
+                         "fp32 runs)")
     ap.add_argument("--physics-companion", default="auto", choices=("auto", "on", "off"),
-                    help="also time the 512^3 CPML + TF/SF, Drude and Drude + UPML configs and report them "
-                         "under 'physics' (auto: one GPU, fp32 runs)")
+                    help="with --full: also time the 512^3 CPML + TF/SF, Drude and Drude + UPML configs and report "
+                         "them under 'physics' (auto: one GPU, fp32 runs)")
     ap.add_argument("--physics-steps", type=int, default=30, help="timed steps (rounded up to whole passes)")
     ap.add_argument("--physics-warmup", type=int, default=45,
                     help="untimed steps before the physics configs' timed ones (hybrid passes capture their HIP "
@@ -337,6 +385,8 @@ def main(argv=None) -> int:
     ap.add_argument("--tb-xcd", type=int, default=0, help="XCD-aware tile order of the blocked kernel (1 on, 0 off)")
     ap.add_argument("--timeout", type=float, default=300.0, help="collective timeout (s): a hung exchange aborts")
     a = ap.parse_args(argv)
+    if not a.full and "on" in (a.fp64_companion, a.physics_companion):
+        ap.error("the companions run under --full")
 
     import torch
     import torch.distributed as dist
@@ -346,6 +396,8 @@ def main(argv=None) -> int:
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    if a.dump_outputs and world > 1:
+        ap.error("--dump-outputs needs a single-rank run")
     if world != a.gpus and rank == 0:
         print("warning: --gpus %d but WORLD_SIZE %d; using WORLD_SIZE" % (a.gpus, world), file=sys.stderr)
     backend, device = resolve_backend(a.backend, "auto")
@@ -367,18 +419,19 @@ def main(argv=None) -> int:
     size = tuple(a.size)
     core = parse_topology(a.topology, size, world, a.time_block != 1) if world > 1 else None
     topo = core.topology if core is not None else (1, 1, 1)
-    res = run_one(a, a.dtype, world, rank, device, backend, core)
+    res = run_one(a, a.dtype, world, rank, device, backend, core, dump_dir=a.dump_outputs)
     fp64 = None
     companion = a.fp64_companion == "on" or (a.fp64_companion == "auto" and world == 1 and a.dtype == "f32"
                                               and backend == "hip")
-    if companion:
+    if a.full and companion:
         try:
             fp64 = run_one(a, "f64", world, rank, device, backend, core)
         except Exception as e:  # the headline line must still be printed
             fp64 = {"error": "%s: %s" % (type(e).__name__, e)}
     physics = None
-    if a.physics_companion == "on" or (a.physics_companion == "auto" and world == 1 and a.dtype == "f32"
-                                       and backend == "hip"):
+    companion = a.physics_companion == "on" or (a.physics_companion == "auto" and world == 1 and a.dtype == "f32"
+                                                 and backend == "hip")
+    if a.full and companion:
         physics = {}
         for name, desc, args in PHYSICS_CONFIGS:
             try:

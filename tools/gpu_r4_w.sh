@@ -21,6 +21,6 @@ for cfg in "cpml_tfsf:--scene vacuum --use-pml --pml-type cpml --use-tfsf" "upml
   run ${lab}_graph $args || exit 1
   run ${lab}_nograph $args --hybrid-graph off || exit 1
 done
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --fp64-companion off > $O/bench.log 2>&1 || { echo "bench failed"; tail -3 $O/bench.log; exit 1; }
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --fp64-companion off > $O/bench.log 2>&1 || { echo "bench failed"; tail -3 $O/bench.log; exit 1; }
 tail -1 $O/bench.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], {k: v["value"] for k, v in d["physics"].items()})'
 echo done

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r6m
 mkdir -p $O
 s=$(date +%s)
-timeout -k 10 900 python bench.py > $O/bench.log 2>&1 || { echo bench failed; tail -5 $O/bench.log; exit 1; }
+timeout -k 10 900 python bench.py --full > $O/bench.log 2>&1 || { echo bench failed; tail -5 $O/bench.log; exit 1; }
 e=$(date +%s)
 echo "bench wall $((e - s)) s"
 tail -1 $O/bench.log | python3 -c "

@@ -18,7 +18,7 @@ for cfg in "c3:$C3" "dr:$DR" "du:$DR --use-pml"; do
   echo "f64 $lab: native $(grep -o '"mcells_per_s": [0-9.]*' $O/nat_$lab.log | cut -d' ' -f2)  python $(grep -o '"mcells_per_s": [0-9.]*' $O/py_$lab.log | cut -d' ' -f2)"
 done
 s=$(date +%s)
-timeout -k 10 900 python bench.py > $O/bench.log 2>&1 || { echo bench failed; tail -5 $O/bench.log; exit 1; }
+timeout -k 10 900 python bench.py --full > $O/bench.log 2>&1 || { echo bench failed; tail -5 $O/bench.log; exit 1; }
 e=$(date +%s)
 echo "bench wall $((e - s)) s"
 tail -1 $O/bench.log | python3 -c "

@@ -9,7 +9,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 240 --timeout-me
 tail -1 $O/tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo smoke failed; tail -5 $O/smoke.log; exit 1; }
 echo smoke ok
-timeout -k 10 900 python bench.py > $O/bench.log 2>&1 || { echo bench failed; tail -5 $O/bench.log; exit 1; }
+timeout -k 10 900 python bench.py --full > $O/bench.log 2>&1 || { echo bench failed; tail -5 $O/bench.log; exit 1; }
 tail -1 $O/bench.log | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
