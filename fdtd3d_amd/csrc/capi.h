@@ -191,4 +191,12 @@ int fdtd_amplitude_many_f32(const void* const* f, void* const* amp, int ncomp, i
                             long long amp_xs, double accuracy, unsigned int* changed, void* s);
 int fdtd_amplitude_many_f64(const void* const* f, void* const* amp, int ncomp, int ny, int nz, const int* boxes,
                             long long amp_xs, double accuracy, unsigned int* changed, void* s);
+
+// running DFT monitors (dft_kernels.hip): one sample of every entry of a
+// monitor in one launch.  tab = n device entries of fdtd_dft_ent_size() bytes,
+// tw = host [2 kinds][K][cos, sin], 1 <= K <= fdtd_dft_max_k()
+int fdtd_dft_accum_f32(const void* tab, int n, int nblocks, int K, const double* tw, void* s);
+int fdtd_dft_accum_f64(const void* tab, int n, int nblocks, int K, const double* tw, void* s);
+int fdtd_dft_ent_size();
+int fdtd_dft_max_k();
 }

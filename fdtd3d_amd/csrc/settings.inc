@@ -144,5 +144,17 @@ FDTD_INT (shellStreams, "--shell-streams", 0, "Hybrid passes: HIP streams the in
 FDTD_STRING (hybridGraph, "--hybrid-graph", "auto", "2D hybrid passes re-issued from a launch record once recorded (auto; graph = replayed from HIP graphs; off = planned every pass)")
 FDTD_STRING (hybridTfsf, "--hybrid-tfsf", "auto", "Hybrid passes with TF/SF: where the TF/SF faces are corrected (auto / core = inside the blocked core pass when the incidence is along x or y, the stepped shell then only covers the absorbing layers; shell = the faces lie in the stepped shell; split = the x faces in the shell, the y / z faces in the core, which runs the TF/SF variant only on its y / z border slabs)")
 FDTD_STRING (blockedDrude, "--blocked-drude", "auto", "Drude media (electric, uniform eps / gamma, 3D; fp32 and fp64, the native driver fp32): advance the dispersive box inside the blocked passes, its D / E history in registers (auto / on = also the torch oracle; off = the stepped dispersive box of the hybrid plan)")
+
+/* ---- extensions: running-DFT field monitors (models/dft.py; Python driver) ---- */
+FDTD_BOOL (doUseDft, "--use-dft", "Accumulate a running discrete Fourier transform of the fields on a box (amplitude and phase at every monitored wavelength from one real-valued run)")
+FDTD_STRING (dftWavelengths, "--dft-wavelengths", "", "Monitored free-space wavelengths (m), comma separated, at most 8; empty = the source wavelength")
+FDTD_INT (dftStep, "--dft-step", 0, "Steps between DFT samples; 0 = automatic (the largest multiple of the blocked pass length with at least 8 samples per shortest monitored period)")
+FDTD_INT (dftStart, "--dft-start", 0, "First step at which the DFT monitor samples")
+FDTD_INT (dftSizeX, "--dft-sizex", 0, "Distance (cells) of the DFT monitor box from both x borders (0 = the whole grid)")
+FDTD_INT (dftSizeY, "--dft-sizey", 0, "Distance (cells) of the DFT monitor box from both y borders")
+FDTD_INT (dftSizeZ, "--dft-sizez", 0, "Distance (cells) of the DFT monitor box from both z borders")
+FDTD_ACTION ("--same-size-dft", "Copy the x DFT monitor distance to y and z")
+FDTD_STRING (dftHTime, "--dft-h-time", "half", "Sample time of the H components in the DFT phase reference: half (their own time, half a step after E) or same (the E time)")
+FDTD_BOOL (doUseNtffDft, "--ntff-dft", "With --use-ntff: monitor the NTFF surface slabs at the source wavelength and print the diagram of the phasors at the end of the run")
 FDTD_BOOL (doPrintJson, "--json", "Print a JSON summary line after the run")
 FDTD_INT (warmupSteps, "--warmup-steps", 0, "Untimed time steps run before the timed loop (benchmarking; they advance the simulation)")

@@ -113,6 +113,8 @@ SettingsStatus Settings::parse(const std::vector<std::string>& t, bool is_cmd) {
       tfsfSizeY = tfsfSizeZ = tfsfSizeX;
     } else if (a == "--same-size-ntff") {
       ntffSizeY = ntffSizeZ = ntffSizeX;  // reference bug Settings.cpp:133-136 fixed
+    } else if (a == "--same-size-dft") {
+      dftSizeY = dftSizeZ = dftSizeX;
     } else if (a == "--same-size-topology") {
       topologySizeY = topologySizeZ = topologySizeX;
     } else if (a == "--1d") {

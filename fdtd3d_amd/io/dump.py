@@ -154,6 +154,51 @@ def dump_fields(scheme, settings, step: int, name_prefix: str = "", scattered: b
     return files
 
 
+def dump_dft(scheme, monitor, settings, step: int, directory: Optional[str] = None) -> List[str]:
+    """The phasors of a DFT monitor (models/dft.py), every selected component
+    and wavelength index, as ``-Re`` / ``-Im`` / ``-Mod`` grids named
+    ``DFT<k>-<comp>`` in the chosen formats.  Decomposed runs write each
+    rank's owned part of the box (``--gather-full-grid``: rank 0 the whole
+    box)."""
+    from .naming import dft_name
+    directory = directory or settings.outputDir
+    rank = scheme.domain.rank
+    gather = settings.doGatherFullGrid and scheme.halo is not None
+    dim = {"3d": 3, "tmz": 2, "tez": 2, "1d": 1}[scheme.cfg.scheme]
+    files: List[str] = []
+    wanted = selected_components(settings, scheme.comps)
+    for i, (c, _) in enumerate(monitor.requests):
+        if c not in wanted:
+            continue
+        for k in range(len(monitor.wavelengths)):
+            ph = monitor.gather(scheme, i, k) if gather else monitor.phasor(i, k)
+            if ph is None or ph.numel() == 0:
+                continue
+            re, im = ph.real.contiguous(), ph.imag.contiguous()
+            parts = (("Re", re), ("Im", im), ("Mod", ph.abs()))
+            for fmt in formats(settings):
+                if fmt == "dat":
+                    for part, g in parts:
+                        files += DATDumper(step, GridFileType.CURRENT, rank, dft_name(k, c, part),
+                                           directory).dump_grid(g)
+                elif fmt == "txt":
+                    for part, g in parts:
+                        files += TXTDumper(step, GridFileType.CURRENT, rank, dft_name(k, c, part),
+                                           directory).dump_grid(g, dim=dim)
+                else:
+                    d = BMPDumper(step, GridFileType.CURRENT, rank, dft_name(k, c), directory, settings.dumperPalette,
+                                  settings.dumperOrthAxis)
+                    if dim == 3:
+                        ax = settings.dumperOrthAxis
+                        mid = re.shape[ax] // 2
+                        start, end = [0, 0, 0], list(re.shape)
+                        start[ax], end[ax] = mid, mid + 1
+                        files += d.dump_grid(re, im, start, end, dim=3)
+                    else:
+                        files += d.dump_grid(re, im, dim=dim)
+    return files
+
+
 def dump_materials(scheme, settings, directory: Optional[str] = None) -> List[str]:
     """Eps / Mu (and Drude omega/gamma with metamaterials) on the eps layout of
     the local region (reference ``initGrids`` dumps)."""

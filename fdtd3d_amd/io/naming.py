@@ -27,6 +27,13 @@ def grid_file_name(step: int, level: GridFileType, rank: int, name: str, directo
     return os.path.join(directory, "%s[%d]_rank-%d_%s" % (_PREFIX[level], int(step), int(rank), name))
 
 
+def dft_name(k: int, comp: str, part: str = "") -> str:
+    """Grid name of a DFT monitor's phasor: ``DFT<k>-<comp>`` for wavelength
+    index ``k`` (``part``: ``Re`` / ``Im`` / ``Mod`` for the formats that do
+    not add it themselves)."""
+    return "DFT%d-%s%s" % (int(k), comp, "-" + part if part else "")
+
+
 def levels(kind: GridFileType):
     """File levels written for a dump type."""
     if kind == GridFileType.ALL:

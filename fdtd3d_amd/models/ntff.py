@@ -20,7 +20,9 @@ Differences from the reference, all deliberate:
 * the box is set by ``--ntff-size{x,y,z}`` (the reference hard-codes 13 cells,
   ``Scheme3D.h:231-232``, and ignores the option);
 * real-valued runs are handled as complex fields with zero imaginary part
-  (the reference only builds 3D with complex values).
+  (the reference only builds 3D with complex values): the diagram of a
+  snapshot.  ``--ntff-dft`` (:func:`ntff_report_dft`) gives the diagram of the
+  time-harmonic field from the phasors of a running-DFT monitor instead.
 
 Tangential fields are brought to the face-cell centres by averaging the two
 (H) or four (E) nearest Yee samples.
@@ -218,6 +220,28 @@ def ntff_report(scheme, t: int, out=None) -> Optional[torch.Tensor]:
         im = {c: scheme.owned_field(c, 1) for c in comps} if scheme.planes == 2 else None
         p = ntff_power(re, im, scheme.cfg.size, scheme.cfg.ntff_size, scheme.dx, scheme.wavelength,
                        scheme.layout.theta, phis)
+    for a, v in zip(phis.tolist(), p.cpu().tolist()):
+        out.write("=== t=%u, inc angle=%f; angle %f === %.17g \n" % (t, scheme.layout.phi, a, v))
+    return p
+
+
+def ntff_report_dft(scheme, monitor, t: int, out=None, k: int = 0) -> Optional[torch.Tensor]:
+    """The diagram of the time-harmonic field from the phasors of a running-
+    DFT monitor over the ``ntff_requests`` slabs (models/dft.py; ``--ntff-dft``)
+    at its wavelength ``k``, printed with the same report lines.  A real-valued
+    run's :func:`ntff_report` is the diagram of a snapshot instead.  Decomposed
+    runs gather the slabs' phasors on rank 0 (None elsewhere)."""
+    import sys
+    out = out or sys.stdout
+    phis = reference_angles()
+    req = ntff_requests(scheme.cfg.size, scheme.cfg.ntff_size)
+    slabs = {key: monitor.gather(scheme, key, k) for key in req}
+    if any(v is None for v in slabs.values()):
+        return None
+    re = {key: v.real for key, v in slabs.items()}
+    im = {key: v.imag for key, v in slabs.items()}
+    p = ntff_power(re, im, scheme.cfg.size, scheme.cfg.ntff_size, scheme.dx, monitor.wavelengths[k],
+                   scheme.layout.theta, phis, boxes=True)
     for a, v in zip(phis.tolist(), p.cpu().tolist()):
         out.write("=== t=%u, inc angle=%f; angle %f === %.17g \n" % (t, scheme.layout.phi, a, v))
     return p

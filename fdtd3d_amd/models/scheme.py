@@ -116,6 +116,13 @@ class SchemeConfig:
     dispersion: str = "drude"                # drude | lorentz (metamaterial regions)
     lorentz_omega0_ratio: float = 0.5        # Lorentz resonance / source frequency
     amplitude_check_steps: int = 8           # amplitude mode: steps between host reads of the changed counts
+    use_dft: bool = False                    # running-DFT monitor on a box (models/dft.py)
+    dft_wavelengths: str = ""                # comma-separated metres; empty = the source wavelength
+    dft_step: int = 0                        # steps between samples; 0 = automatic (models/dft.py auto_step)
+    dft_start: int = 0
+    dft_size: Tuple[int, int, int] = (0, 0, 0)  # distance of the monitor box from the borders (0 = whole grid)
+    dft_h_time: str = "half"                 # H sample time: half (its own) | same (the E time)
+    ntff_dft: bool = False                   # with use_ntff: monitor the NTFF slabs, diagram from the phasors
 
     @classmethod
     def from_settings(cls, s) -> "SchemeConfig":
@@ -147,7 +154,9 @@ class SchemeConfig:
             amplitude_check_steps=s.amplitudeCheckSteps,
             hybrid_block=s.hybridBlock, shell_streams=s.shellStreams, hybrid_graph=s.hybridGraph,
             hybrid_tfsf=s.hybridTfsf, blocked_drude=s.blockedDrude,
-            profile_phases=s.doProfilePhases, use_hip_graph=s.doUseHipGraph)
+            profile_phases=s.doProfilePhases, use_hip_graph=s.doUseHipGraph,
+            use_dft=s.doUseDft, dft_wavelengths=s.dftWavelengths, dft_step=s.dftStep, dft_start=s.dftStart,
+            dft_size=(s.dftSizeX, s.dftSizeY, s.dftSizeZ), dft_h_time=s.dftHTime, ntff_dft=s.doUseNtffDft)
 
 
 def _drude_coefs(dt: float, e0: float, eps, w, g, q: float):

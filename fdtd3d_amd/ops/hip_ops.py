@@ -673,6 +673,75 @@ class HipOps:
     def box_ent_size(self) -> int:
         return int(self.lib.fdtd_box_ent_size())
 
+    # ----------------------------------------------------------- DFT monitors
+    def _dft_table(self, entries):
+        """(device table, entries, blocks) of a monitor's non-empty entries
+        with their current field arrays; every box checked against its array."""
+        import numpy as np
+        from .dft import DFT_ENT_SIZE, DFT_MAX_K, acc_shape, vec_width, z_pad
+        if not 1 <= entries.k <= DFT_MAX_K:
+            raise HipError("dft_accumulate: 1..%d frequencies, got %d" % (DFT_MAX_K, entries.k))
+        if int(self.lib.fdtd_dft_ent_size()) != DFT_ENT_SIZE or int(self.lib.fdtd_dft_max_k()) != DFT_MAX_K:
+            raise HipError("DftEnt layout mismatch")
+        v = vec_width(self.dtype)
+        rows = []
+        blk = 0
+        for e in entries:
+            if e.empty:
+                continue
+            self._check_tensor(e.field)
+            self._check_tensor(e.acc, acc_shape(e.box, entries.k, v))
+            if e.field.dim() != 3:
+                raise HipError("dft_accumulate: 3D field arrays")
+            for d in range(3):
+                if e.box[0][d] < 0 or e.box[1][d] > e.field.shape[d]:
+                    raise HipError("dft_accumulate: box %s outside array %s" % (e.box, tuple(e.field.shape)))
+            if e.kind not in (0, 1):
+                raise HipError("dft_accumulate: kind 0 (E) or 1 (H)")
+            if e.acc.data_ptr() % 16:
+                raise HipError("dft_accumulate: accumulators must be 16-byte aligned")
+            groups = (e.box[1][0] - e.box[0][0]) * (e.box[1][1] - e.box[0][1]) * (z_pad(e.box, v)[1] // v)
+            nb = -(-groups // 256)
+            if groups >= 2 ** 31 - 256 or blk + nb >= 2 ** 31:
+                raise HipError("dft_accumulate: monitor too large for one launch")
+            vec = e.field.shape[2] % v == 0 and e.field.data_ptr() % 16 == 0
+            rows.append((e, blk, 1 if vec else 0))
+            blk += nb
+        if not rows:
+            return None
+        e64 = np.zeros((len(rows), 8), dtype=np.int64)
+        e32 = e64.view(np.int32)
+        for r, (e, b0, vec) in enumerate(rows):
+            e64[r, 0] = e.field.data_ptr()
+            e64[r, 1] = e.acc.data_ptr()
+            e32[r, 4], e32[r, 5] = e.field.shape[1], e.field.shape[2]
+            e32[r, 6:9] = e.box[0]
+            e32[r, 9:12] = e.box[1]
+            e32[r, 12], e32[r, 13], e32[r, 14] = b0, e.kind, vec
+        return (torch.from_numpy(e64).to(self.device), len(rows), blk)
+
+    def dft_accumulate(self, entries, twiddles) -> None:
+        """One sample of a running-DFT monitor (ops/dft.py ``DftEntries``) in
+        ONE launch over all its entries (dft_kernels.hip k_dft_accum):
+        ``re[k] += f cos``, ``im[k] += f sin`` with ``twiddles[kind][k] =
+        (cos, sin)`` passed by value.  The device table is cached on the
+        monitor per set of field arrays (F / F_alt ping-pong: the current
+        arrays are looked up at every call)."""
+        key = tuple((e.field.data_ptr(), tuple(e.field.shape), e.acc.data_ptr(), e.box, e.kind) for e in entries)
+        tab = entries.tables.get(key, False)
+        if tab is False:
+            tab = entries.tables[key] = self._dft_table(entries)
+        if len(twiddles) != 2 or any(len(row) != entries.k or any(len(cs) != 2 for cs in row) for row in twiddles):
+            raise HipError("dft_accumulate: twiddles of shape (2, %d, 2)" % entries.k)
+        if tab is None:
+            return
+        table, n, nblocks = tab
+        flat = [float(x) for row in twiddles for cs in row for x in cs]
+        rc = self.fn("dft_accum")(_ptr(table), c_int(n), c_int(nblocks), c_int(entries.k),
+                                  (c_double * len(flat))(*flat), _stream())
+        _check(rc, "dft_accum")
+        self.launches += 1
+
     def unpack(self, tensors: Sequence[torch.Tensor], box: Box, buf: torch.Tensor) -> None:
         shape = tuple(tensors[0].shape)
         n = 1

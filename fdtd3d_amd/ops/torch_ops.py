@@ -553,6 +553,31 @@ class TorchOps:
         flat = target.view(-1)
         flat.index_add_(0, table.off, v.to(target.dtype))
 
+    def dft_accumulate(self, entries, twiddles) -> None:
+        """One sample of a running-DFT monitor (ops/dft.py ``DftEntries``):
+        per entry and frequency k ``re[k] += f cos``, ``im[k] += f sin`` with
+        ``twiddles[kind][k] = (cos, sin)`` (fp64 on the host, rounded to the
+        accumulators' precision).  The oracle of csrc/dft_kernels.hip."""
+        import numpy as np
+        tw = np.asarray(twiddles, dtype=np.float64)
+        if tw.shape != (2, entries.k, 2):
+            raise ValueError("dft_accumulate: twiddles of shape (2, %d, 2), got %s" % (entries.k, tw.shape))
+        for e in entries:
+            if e.empty:
+                continue
+            (x0, y0, z0), (x1, y1, z1) = e.box
+            if min(x0, y0, z0) < 0 or any(e.box[1][d] > e.field.shape[d] for d in range(3)):
+                raise ValueError("dft_accumulate: box %s outside array %s" % (e.box, tuple(e.field.shape)))
+            f = e.field[x0:x1, y0:y1, z0:z1]
+            acc = e.owned()
+            if e.acc.dtype == torch.float32:
+                tw_e = tw[e.kind].astype(np.float32)
+            else:
+                tw_e = tw[e.kind]
+            for k in range(entries.k):
+                acc[k, 0] += f * float(tw_e[k, 0])
+                acc[k, 1] += f * float(tw_e[k, 1])
+
 
 class TfsfTable:
     """Per-component TF/SF correction list: ``target[off] += coef *

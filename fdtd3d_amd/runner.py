@@ -23,7 +23,7 @@ import time
 from typing import List, Optional
 
 from .utils import logging as log
-from .utils.settings import (EXIT_BREAK_ARG_PARSING, EXIT_OK, Settings, setup_from_cmd)
+from .utils.settings import (EXIT_BREAK_ARG_PARSING, EXIT_ERROR, EXIT_OK, Settings, setup_from_cmd)
 
 
 def select_device_index(settings: Settings, local_rank: int, world: int, avail: int) -> int:
@@ -163,6 +163,15 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
     if status != EXIT_OK:
         return status
     log.set_level(settings.logLevel)
+    if settings.doUseDft or settings.doUseNtffDft:
+        # refused before anything is set up, never a silent fallback (models/dft.py)
+        from .models.dft import refuse_config
+        from .models.scheme import SchemeConfig
+        why = refuse_config(SchemeConfig.from_settings(settings),
+                            checkpoints=bool(settings.checkpointDir or settings.loadFromFile))
+        if why:
+            out.write("ERROR: %s\n" % why)
+            return EXIT_ERROR
     dist, rank, world = _init_distributed(settings)
     log.set_rank(rank)
     import torch
@@ -208,6 +217,10 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         scheme.add_periodic(settings.intermediateSaveStep, 0, interm_hook)
     if settings.checkpointDir and settings.checkpointStep > 0:
         scheme.add_periodic(settings.checkpointStep, 0, checkpoint_hook)
+    monitors = {}
+    if scheme.cfg.use_dft or scheme.cfg.ntff_dft:
+        from .models.dft import monitors_from_config
+        monitors = monitors_from_config(scheme)  # running DFTs, sampled between passes
     steps = max(0, settings.numTimeSteps - start_step)
 
     def sync():
@@ -239,6 +252,13 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         dump_fields(scheme, settings, scheme.t)
     if settings.doSaveScatteredFieldRes:
         dump_fields(scheme, settings, scheme.t, "scattered-", scattered=True)
+    if "box" in monitors and settings.doSaveRes:
+        from .io.dump import dump_dft
+        dump_dft(scheme, monitors["box"], settings, scheme.t)
+    if "ntff" in monitors:
+        # the diagram of the time-harmonic field, from the NTFF slabs' phasors
+        from .models.ntff import ntff_report_dft
+        ntff_report_dft(scheme, monitors["ntff"], scheme.t, out=out if rank == 0 else open(os.devnull, "w"))
     if settings.checkpointDir:
         save_checkpoint(scheme, settings.checkpointDir)
     phases = scheme.prof.summary() if scheme.prof.enabled else None
@@ -262,6 +282,10 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                    "ranks": world, "backend": scheme.ops.name}
             if phases:
                 rec["phases"] = phases
+            if monitors:
+                rec["dft"] = monitors["box" if "box" in monitors else "ntff"].info()
+                if len(monitors) == 2:
+                    rec["dft"]["ntff"] = monitors["ntff"].info()
             if breakdown is not None:
                 rec["rank0_passes"] = breakdown  # decomposed passes: interior / exchange wait / shell ms
             if scheme.device.type == "cuda":

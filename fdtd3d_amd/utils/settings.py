@@ -186,6 +186,8 @@ class Settings:
             self.tfsfSizeY = self.tfsfSizeZ = self.tfsfSizeX
         elif a == "--same-size-ntff":
             self.ntffSizeY = self.ntffSizeZ = self.ntffSizeX
+        elif a == "--same-size-dft":
+            self.dftSizeY = self.dftSizeZ = self.dftSizeX
         elif a == "--same-size-topology":
             self.topologySizeY = self.topologySizeZ = self.topologySizeX
         elif a == "--1d":
@@ -251,6 +253,8 @@ class Settings:
             raise SettingsError("--dispersion must be drude or lorentz")
         if self.sourceType not in ("sine", "gaussian"):
             raise SettingsError("--source must be sine or gaussian")
+        if self.dftHTime not in ("half", "same"):
+            raise SettingsError("--dft-h-time must be half or same")
         if self.bufferSize < 1:
             raise SettingsError("--buffer-size must be >= 1")
         for n in ("sizeX", "sizeY", "sizeZ"):
