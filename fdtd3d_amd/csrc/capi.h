@@ -50,6 +50,10 @@ int fdtd_chain3d_f32(const void* const* P, const double* S, const int* I, int dr
                      void* stream);
 int fdtd_chain3d_f64(const void* const* P, const double* S, const int* I, int drude, int kind_e, int ny, int nz,
                      void* stream);
+// A/B knobs of the non-dispersive chain launches: the float4 form (fp32, full-grid levels; off by
+// default), and one component per thread (1, the default) or all three (0); -1 = FDTD3D_CHAIN_SPLIT
+void fdtd_set_chain_v4(int on);
+void fdtd_set_chain_split(int mode);
 // TF/SF: 1D incident line steps and the table-driven corrections
 // (generic_kernels.hip; ijk may be null when the box holds every target)
 int fdtd_inc_e_f32(float* einc, const float* hinc, int n, double c, double src, void* stream);

@@ -622,6 +622,10 @@ FDTD_API int fdtd_chain3d_f64(const void* const* P, const double* S, const int* 
 
 FDTD_API void fdtd_set_chain_v4(int on) { g_chain_v4 = on != 0; }
 
+// non-dispersive chain launches: 1 one component per thread (k_chain3d_c), 0 all three
+// (k_chain3d), -1 back to FDTD3D_CHAIN_SPLIT / the default
+FDTD_API void fdtd_set_chain_split(int mode) { g_chain_split = mode < 0 ? -1 : (mode != 0); }
+
 // layout of the chain launch tables (checked by the callers that build them)
 FDTD_API int fdtd_chain_ints_per_comp() { return CI_PER; }
 FDTD_API int fdtd_chain_ptrs_per_comp() { return CP_PER; }

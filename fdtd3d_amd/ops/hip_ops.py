@@ -1446,6 +1446,13 @@ class HipOps:
     chain_fold = True  # thin plain boxes next to a z PML slab ride in the slab's chain launch
     region_aux = True  # chain launches address region-local D / D1 levels (models/regions.py)
 
+    def set_chain_split(self, mode: int) -> None:
+        """Non-dispersive chain launches of the library (every ops object of
+        the process): 1 one component per thread (k_chain3d_c, the default), 0
+        the three components of a cell per thread (k_chain3d), -1 back to
+        FDTD3D_CHAIN_SPLIT / the default."""
+        self.lib.fdtd_set_chain_split(c_int(int(mode)))
+
     def _drude_lut(self, st: dict, dr, shape):
         """(uint8 id array, (n, 5) table) of a component's five Drude
         coefficient arrays, built once per component (None, None when the
