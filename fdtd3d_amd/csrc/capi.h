@@ -203,4 +203,14 @@ int fdtd_dft_accum_f32(const void* tab, int n, int nblocks, int K, const double*
 int fdtd_dft_accum_f64(const void* tab, int n, int nblocks, int K, const double* tw, void* s);
 int fdtd_dft_ent_size();
 int fdtd_dft_max_k();
+
+// Poynting-flux face sums from DFT accumulators (flux_kernels.hip): tab = n
+// device entries of fdtd_flux_ent_size() bytes ordered by face, fblk = F + 1
+// device ints (first block of every face), partials = nblocks x K doubles of
+// scratch, out = F x K doubles
+int fdtd_flux_eval_f32(const void* tab, int n, int nblocks, int K, const void* fblk, int F, void* partials, void* out,
+                       void* s);
+int fdtd_flux_eval_f64(const void* tab, int n, int nblocks, int K, const void* fblk, int F, void* partials, void* out,
+                       void* s);
+int fdtd_flux_ent_size();
 }

@@ -156,5 +156,12 @@ FDTD_INT (dftSizeZ, "--dft-sizez", 0, "Distance (cells) of the DFT monitor box f
 FDTD_ACTION ("--same-size-dft", "Copy the x DFT monitor distance to y and z")
 FDTD_STRING (dftHTime, "--dft-h-time", "half", "Sample time of the H components in the DFT phase reference: half (their own time, half a step after E) or same (the E time)")
 FDTD_BOOL (doUseNtffDft, "--ntff-dft", "With --use-ntff: monitor the NTFF surface slabs at the source wavelength and print the diagram of the phasors at the end of the run")
+/* ---- extensions: Poynting-flux monitor on a closed box (models/flux.py; Python driver) ---- */
+FDTD_BOOL (doUseFlux, "--use-flux", "Monitor the time-averaged power through the six faces of a box from running-DFT phasors (3D; wavelengths, step and start from --dft-wavelengths, --dft-step, --dft-start): radiated, scattered or absorbed power and, with TF/SF, the cross-section per wavelength")
+FDTD_INT (fluxSizeX, "--flux-sizex", 0, "Distance (cells) of the flux box from both x borders")
+FDTD_INT (fluxSizeY, "--flux-sizey", 0, "Distance (cells) of the flux box from both y borders")
+FDTD_INT (fluxSizeZ, "--flux-sizez", 0, "Distance (cells) of the flux box from both z borders")
+FDTD_ACTION ("--same-size-flux", "Copy the x flux box distance to y and z")
+FDTD_INT (fluxReportStep, "--flux-report-step", 0, "Steps between flux reports; 0 = only at the end of the run")
 FDTD_BOOL (doPrintJson, "--json", "Print a JSON summary line after the run")
 FDTD_INT (warmupSteps, "--warmup-steps", 0, "Untimed time steps run before the timed loop (benchmarking; they advance the simulation)")

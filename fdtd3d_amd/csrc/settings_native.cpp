@@ -115,6 +115,8 @@ SettingsStatus Settings::parse(const std::vector<std::string>& t, bool is_cmd) {
       ntffSizeY = ntffSizeZ = ntffSizeX;  // reference bug Settings.cpp:133-136 fixed
     } else if (a == "--same-size-dft") {
       dftSizeY = dftSizeZ = dftSizeX;
+    } else if (a == "--same-size-flux") {
+      fluxSizeY = fluxSizeZ = fluxSizeX;
     } else if (a == "--same-size-topology") {
       topologySizeY = topologySizeZ = topologySizeX;
     } else if (a == "--1d") {

@@ -94,9 +94,11 @@ def monitor_box_requests(scheme, margin: Sequence[int]) -> List[Request]:
 def refuse_config(cfg, checkpoints: bool = False) -> Optional[str]:
     """Why the configuration cannot run with its DFT monitors (None: it can).
     Never a silent fallback."""
-    if not (cfg.use_dft or cfg.ntff_dft):
+    if not (cfg.use_dft or cfg.ntff_dft or cfg.use_flux):
         return None
-    flag = "--use-dft" if cfg.use_dft else "--ntff-dft"
+    flag = "--use-dft" if cfg.use_dft else "--ntff-dft" if cfg.ntff_dft else ""
+    if cfg.use_flux:
+        flag = flag + " / --use-flux" if flag else "--use-flux"
     if cfg.complex_values:
         return ("%s with --complex-field-values: a complex run already carries the phasor; the monitor needs a "
                 "real-valued run" % flag)
@@ -107,6 +109,8 @@ def refuse_config(cfg, checkpoints: bool = False) -> Optional[str]:
                 % flag)
     if cfg.ntff_dft and not (cfg.use_ntff and cfg.scheme == "3d"):
         return "--ntff-dft needs --use-ntff on a 3D run"
+    if cfg.use_flux and cfg.scheme != "3d":
+        return "--use-flux needs a 3D run"
     return None
 
 
@@ -246,6 +250,46 @@ class DftMonitor:
             return out
         if rank < core.used_procs and mine.numel():
             dist.send(torch.view_as_real(mine).contiguous(), dst, group=group, tag=202)
+        return None
+
+    def gather_accumulators(self, scheme, key, dst: int = 0) -> Optional[torch.Tensor]:
+        """The raw sums ``(K, 2, bx, by, bz)`` over the whole requested box on
+        rank ``dst`` (None elsewhere), through the halo exchanger's transport;
+        serial runs: :meth:`accumulators`.  Every rank calls it for the same
+        keys in the same order.  What products of phasors are computed from
+        (models/flux.py): the sums travel unscaled and in the run's
+        precision."""
+        i = self.index(key)
+        mine = self.accumulators(i)
+        comm = scheme.halo.comm if scheme.halo is not None else None
+        if comm is None or comm.world == 1:
+            return mine
+        from ..parallel.comm import P2P
+        from ..parallel.topology import ParallelGridCore
+        d = scheme.domain
+        lo, hi = self.requests[i][1]
+        core = ParallelGridCore(tuple(d.global_size), comm.world, tuple(d.topology))
+        head = tuple(mine.shape[:2])
+        if comm.rank == dst:
+            out = torch.zeros(head + tuple(hi[a] - lo[a] for a in range(3)), dtype=mine.dtype, device=mine.device)
+            for r in range(core.used_procs):
+                dr = core.domain(r, d.buffer_size)
+                pp = box_intersect((lo, hi), (dr.lo, dr.hi))
+                if box_empty(pp):
+                    continue
+                if r == comm.rank:
+                    blk = mine
+                else:
+                    blk = torch.empty(head + tuple(pp[1][a] - pp[0][a] for a in range(3)), dtype=mine.dtype,
+                                      device=mine.device)
+                    for w in comm.post([P2P(False, blk, r, 203)]):
+                        w.wait()
+                out[(slice(None), slice(None)) + tuple(slice(pp[0][a] - lo[a], pp[1][a] - lo[a])
+                                                       for a in range(3))] = blk
+            return out
+        if comm.rank < core.used_procs and mine.numel():
+            for w in comm.post([P2P(True, mine.contiguous(), dst, 203)]):
+                w.wait()
         return None
 
     def info(self) -> Dict[str, object]:

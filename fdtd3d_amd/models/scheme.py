@@ -123,6 +123,9 @@ class SchemeConfig:
     dft_size: Tuple[int, int, int] = (0, 0, 0)  # distance of the monitor box from the borders (0 = whole grid)
     dft_h_time: str = "half"                 # H sample time: half (its own) | same (the E time)
     ntff_dft: bool = False                   # with use_ntff: monitor the NTFF slabs, diagram from the phasors
+    use_flux: bool = False                   # Poynting flux through a closed box from DFT phasors (models/flux.py)
+    flux_size: Tuple[int, int, int] = (0, 0, 0)  # distance of the flux box from the borders
+    flux_report_step: int = 0                # steps between flux reports; 0 = only at the end
 
     @classmethod
     def from_settings(cls, s) -> "SchemeConfig":
@@ -156,7 +159,9 @@ class SchemeConfig:
             hybrid_tfsf=s.hybridTfsf, blocked_drude=s.blockedDrude,
             profile_phases=s.doProfilePhases, use_hip_graph=s.doUseHipGraph,
             use_dft=s.doUseDft, dft_wavelengths=s.dftWavelengths, dft_step=s.dftStep, dft_start=s.dftStart,
-            dft_size=(s.dftSizeX, s.dftSizeY, s.dftSizeZ), dft_h_time=s.dftHTime, ntff_dft=s.doUseNtffDft)
+            dft_size=(s.dftSizeX, s.dftSizeY, s.dftSizeZ), dft_h_time=s.dftHTime, ntff_dft=s.doUseNtffDft,
+            use_flux=s.doUseFlux, flux_size=(s.fluxSizeX, s.fluxSizeY, s.fluxSizeZ),
+            flux_report_step=s.fluxReportStep)
 
 
 def _drude_coefs(dt: float, e0: float, eps, w, g, q: float):

@@ -7,6 +7,10 @@ extent is the box's z range widened to the field's 16-byte groups (from ``lo &
 ~(V - 1)`` to ``hi`` rounded up, ``V`` = 4 fp32 / 2 fp64 elements): an
 accumulator vector and its field vector start at the same z (csrc/
 dft_kernels.hip).  The padded cells are never written and stay zero.
+
+``FluxTerms`` describe what ``dft_flux(terms)`` evaluates from such
+accumulators: products of face-centre averages summed over the faces of a box
+(models/flux.py; csrc/flux_kernels.hip).
 """
 
 from __future__ import annotations
@@ -83,6 +87,77 @@ class DftEntries:
         self.rows.append(e)
         self.tables.clear()
         return e
+
+    def __iter__(self):
+        return iter(self.rows)
+
+    def __len__(self):
+        return len(self.rows)
+
+
+# ------------------------------------------------------------------ flux terms
+FLUX_ENT_SIZE = 112  # bytes of a device table entry of ``dft_flux`` (fdtd_flux_ent_size)
+
+
+class FluxOperand:
+    """One factor of a flux product: ``acc`` = accumulators in the padded
+    ``acc_shape`` layout ``[k][re|im][x][y][z']``, ``first`` = the accumulator
+    index of the first sample of the first face cell per axis, ``avg`` = per
+    axis whether the face-centre value averages the samples ``first`` and
+    ``first + 1`` (models/ntff.py ``_sample_plan``)."""
+    __slots__ = ("acc", "first", "avg")
+
+    def __init__(self, acc: torch.Tensor, first, avg):
+        self.acc = acc
+        self.first = tuple(int(v) for v in first)
+        self.avg = tuple(bool(v) for v in avg)
+
+    def reach_error(self, extent, k: int) -> Optional[str]:
+        """Why the operand's samples for a face of ``extent`` cells leave its
+        accumulator block (None: they do not)."""
+        if self.acc.dim() != 5 or self.acc.shape[0] != k or self.acc.shape[1] != 2:
+            return "accumulators of shape (%d, 2, x, y, z'), got %s" % (k, tuple(self.acc.shape))
+        for a in range(3):
+            last = self.first[a] + extent[a] - 1 + (1 if self.avg[a] else 0)
+            if self.first[a] < 0 or last >= self.acc.shape[2 + a]:
+                return "samples %d..%d along axis %d outside the accumulator block %s" % (
+                    self.first[a], last, a, tuple(self.acc.shape[2:]))
+        return None
+
+
+class FluxTerm:
+    """``sign * sum over the face cells of (Re e Re h + Im e Im h)`` added to
+    row ``face`` of the result; ``extent`` = the face's cells per axis (1
+    along its normal)."""
+    __slots__ = ("face", "sign", "extent", "e", "h")
+
+    def __init__(self, face: int, sign: int, extent, e: FluxOperand, h: FluxOperand):
+        if sign not in (1, -1):
+            raise ValueError("FluxTerm: sign +1 or -1")
+        self.face, self.sign = int(face), int(sign)
+        self.extent = tuple(int(v) for v in extent)
+        self.e, self.h = e, h
+
+    @property
+    def empty(self) -> bool:
+        return any(v <= 0 for v in self.extent)
+
+
+class FluxTerms:
+    """The products of one flux monitor (``ops.dft_flux``) and, on the HIP
+    backend, its cached device table."""
+
+    def __init__(self, k: int, faces: int):
+        self.k, self.faces = int(k), int(faces)
+        self.rows: List[FluxTerm] = []
+        self.table = None
+
+    def add(self, term: FluxTerm) -> FluxTerm:
+        if not 0 <= term.face < self.faces:
+            raise ValueError("FluxTerms: face %d of %d" % (term.face, self.faces))
+        self.rows.append(term)
+        self.table = None
+        return term
 
     def __iter__(self):
         return iter(self.rows)

@@ -742,6 +742,82 @@ class HipOps:
         _check(rc, "dft_accum")
         self.launches += 1
 
+    def _flux_table(self, terms):
+        """(device table, entries, blocks, face block starts, partials) of a
+        flux monitor's non-empty terms, ordered by face; every operand's
+        reach checked against its accumulator block."""
+        import numpy as np
+        from .dft import DFT_MAX_K, FLUX_ENT_SIZE, vec_width
+        if not 1 <= terms.k <= DFT_MAX_K:
+            raise HipError("dft_flux: 1..%d frequencies, got %d" % (DFT_MAX_K, terms.k))
+        if terms.faces < 1:
+            raise HipError("dft_flux: at least one face")
+        if int(self.lib.fdtd_flux_ent_size()) != FLUX_ENT_SIZE:
+            raise HipError("FluxEnt layout mismatch")
+        v = vec_width(self.dtype)
+        rows = []
+        fblk = [0] * (terms.faces + 1)
+        blk = 0
+        for face in range(terms.faces):
+            fblk[face] = blk
+            for t in terms:
+                if t.face != face or t.empty:
+                    continue
+                for op in (t.e, t.h):
+                    self._check_tensor(op.acc)
+                    why = op.reach_error(t.extent, terms.k)
+                    if why:
+                        raise HipError("dft_flux: " + why)
+                    if op.acc.data_ptr() % 16:
+                        raise HipError("dft_flux: accumulators must be 16-byte aligned")
+                    if op.acc[0, 0].numel() >= 2 ** 31:
+                        raise HipError("dft_flux: accumulator block too large")
+                cells = t.extent[0] * t.extent[1] * t.extent[2]
+                nb = -(-cells // 256)
+                if cells >= 2 ** 31 - 256 or blk + nb >= 2 ** 31:
+                    raise HipError("dft_flux: monitor too large for one launch")
+                # z-normal faces: a lane loads the aligned 16-byte group around its z samples
+                zvec = t.extent[2] == 1 and all(op.acc.shape[4] % v == 0 for op in (t.e, t.h))
+                rows.append((t, blk, 1 if zvec else 0))
+                blk += nb
+        fblk[terms.faces] = blk
+        e64 = np.zeros((max(1, len(rows)), FLUX_ENT_SIZE // 8), dtype=np.int64)
+        e32 = e64.view(np.int32)
+        for r, (t, b0, zvec) in enumerate(rows):
+            for c, op in enumerate((t.e, t.h)):
+                nx, ny, nz = op.acc.shape[2:]
+                e64[r, c] = op.acc.data_ptr()
+                e64[r, 2 + c] = nx * ny * nz
+                e32[r, 8 + 2 * c], e32[r, 9 + 2 * c] = ny * nz, nz
+                e32[r, 12 + 3 * c:15 + 3 * c] = op.first
+                e32[r, 21 + c] = sum(1 << a for a in range(3) if op.avg[a])
+            e32[r, 18:21] = t.extent
+            e32[r, 23], e32[r, 24], e32[r, 25], e32[r, 26] = t.face, t.sign, b0, zvec
+        table = torch.from_numpy(e64).to(self.device)
+        fb = torch.tensor(fblk, dtype=torch.int32).to(self.device)
+        partials = torch.empty((max(1, blk), terms.k), dtype=torch.float64, device=self.device)
+        return (table, len(rows), blk, fb, partials)
+
+    def dft_flux(self, terms) -> torch.Tensor:
+        """(faces, K) float64 on the device: per term ``sign * sum over the
+        face cells of (Re e Re h + Im e Im h)`` added to its face's row
+        (ops/dft.py ``FluxTerms``), operands averaged, multiplied and summed
+        in fp64 -- one launch over every term and frequency plus one that
+        folds the blocks' partial sums per face in a fixed order
+        (flux_kernels.hip; no atomics, so the same input gives the same
+        bits).  The device table is cached on ``terms`` (its accumulators are
+        fixed; ``FluxTerms.add`` drops it)."""
+        key = tuple((t.e.acc.data_ptr(), t.h.acc.data_ptr()) for t in terms)
+        if terms.table is None or terms.table[0] != key:
+            terms.table = (key, self._flux_table(terms))
+        table, n, nblocks, fblk, partials = terms.table[1]
+        out = torch.empty((terms.faces, terms.k), dtype=torch.float64, device=self.device)
+        rc = self.fn("flux_eval")(_ptr(table), c_int(n), c_int(nblocks), c_int(terms.k), _ptr(fblk),
+                                  c_int(terms.faces), _ptr(partials), _ptr(out), _stream())
+        _check(rc, "flux_eval")
+        self.launches += 2 if nblocks else 1
+        return out
+
     def unpack(self, tensors: Sequence[torch.Tensor], box: Box, buf: torch.Tensor) -> None:
         shape = tuple(tensors[0].shape)
         n = 1

@@ -578,6 +578,39 @@ class TorchOps:
                 acc[k, 0] += f * float(tw_e[k, 0])
                 acc[k, 1] += f * float(tw_e[k, 1])
 
+    def dft_flux(self, terms) -> torch.Tensor:
+        """(faces, K) float64: per term ``sign * sum over the face cells of
+        (Re e Re h + Im e Im h)`` added to its face's row (ops/dft.py
+        ``FluxTerms``).  Each operand is the face-centre average of its 1, 2
+        or 4 accumulator samples, taken, multiplied and summed in fp64
+        whatever the accumulators' precision.  The oracle of
+        csrc/flux_kernels.hip."""
+        dev = terms.rows[0].e.acc.device if len(terms) else "cpu"
+        out = torch.zeros((terms.faces, terms.k), dtype=torch.float64, device=dev)
+
+        def centre(op, ext):
+            acc, cnt = None, 0
+            for ox in ((0, 1) if op.avg[0] else (0,)):
+                for oy in ((0, 1) if op.avg[1] else (0,)):
+                    for oz in ((0, 1) if op.avg[2] else (0,)):
+                        o = (ox, oy, oz)
+                        sl = tuple(slice(op.first[a] + o[a], op.first[a] + o[a] + ext[a]) for a in range(3))
+                        v = op.acc[(slice(None), slice(None)) + sl].to(torch.float64)
+                        acc = v if acc is None else acc + v
+                        cnt += 1
+            return acc / cnt
+
+        for t in terms:
+            for op in (t.e, t.h):
+                why = None if t.empty else op.reach_error(t.extent, terms.k)
+                if why:
+                    raise ValueError("dft_flux: " + why)
+            if t.empty:
+                continue
+            e, h = centre(t.e, t.extent), centre(t.h, t.extent)
+            out[t.face] += t.sign * (e[:, 0] * h[:, 0] + e[:, 1] * h[:, 1]).sum(dim=(1, 2, 3))
+        return out
+
 
 class TfsfTable:
     """Per-component TF/SF correction list: ``target[off] += coef *

@@ -163,7 +163,7 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
     if status != EXIT_OK:
         return status
     log.set_level(settings.logLevel)
-    if settings.doUseDft or settings.doUseNtffDft:
+    if settings.doUseDft or settings.doUseNtffDft or settings.doUseFlux:
         # refused before anything is set up, never a silent fallback (models/dft.py)
         from .models.dft import refuse_config
         from .models.scheme import SchemeConfig
@@ -221,6 +221,19 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
     if scheme.cfg.use_dft or scheme.cfg.ntff_dft:
         from .models.dft import monitors_from_config
         monitors = monitors_from_config(scheme)  # running DFTs, sampled between passes
+    flux = None
+    if scheme.cfg.use_flux:
+        from .models.flux import flux_from_config
+        flux = flux_from_config(scheme)  # power through a closed box from its own running DFT (models/flux.py)
+
+        def flux_hook(s, t):
+            if halo is not None:
+                halo.drain(s)
+            flux_reported[:] = [t, flux.report(t, out if rank == 0 else open(os.devnull, "w"))]
+
+        flux_reported = [None, None]  # (step, result) of the last periodic report
+        if scheme.cfg.flux_report_step > 0:
+            scheme.add_periodic(scheme.cfg.flux_report_step, 0, flux_hook)
     steps = max(0, settings.numTimeSteps - start_step)
 
     def sync():
@@ -259,6 +272,11 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         # the diagram of the time-harmonic field, from the NTFF slabs' phasors
         from .models.ntff import ntff_report_dft
         ntff_report_dft(scheme, monitors["ntff"], scheme.t, out=out if rank == 0 else open(os.devnull, "w"))
+    flux_result = None
+    if flux is not None and flux_reported[0] == scheme.t:
+        flux_result = flux_reported[1]  # the last step's periodic report is the final one
+    elif flux is not None:
+        flux_result = flux.report(scheme.t, out if rank == 0 else open(os.devnull, "w"))
     if settings.checkpointDir:
         save_checkpoint(scheme, settings.checkpointDir)
     phases = scheme.prof.summary() if scheme.prof.enabled else None
@@ -286,6 +304,8 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                 rec["dft"] = monitors["box" if "box" in monitors else "ntff"].info()
                 if len(monitors) == 2:
                     rec["dft"]["ntff"] = monitors["ntff"].info()
+            if flux_result is not None:
+                rec["flux"] = flux.info(flux_result)
             if breakdown is not None:
                 rec["rank0_passes"] = breakdown  # decomposed passes: interior / exchange wait / shell ms
             if scheme.device.type == "cuda":

@@ -188,6 +188,8 @@ class Settings:
             self.ntffSizeY = self.ntffSizeZ = self.ntffSizeX
         elif a == "--same-size-dft":
             self.dftSizeY = self.dftSizeZ = self.dftSizeX
+        elif a == "--same-size-flux":
+            self.fluxSizeY = self.fluxSizeZ = self.fluxSizeX
         elif a == "--same-size-topology":
             self.topologySizeY = self.topologySizeZ = self.topologySizeX
         elif a == "--1d":
