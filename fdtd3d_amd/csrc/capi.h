@@ -213,4 +213,12 @@ int fdtd_flux_eval_f32(const void* tab, int n, int nblocks, int K, const void* f
 int fdtd_flux_eval_f64(const void* tab, int n, int nblocks, int K, const void* fblk, int F, void* partials, void* out,
                        void* s);
 int fdtd_flux_ent_size();
+
+// sums of squares over boxes of field arrays (energy_kernels.hip): tab = n
+// device entries of fdtd_energy_ent_size() bytes ordered by blk0, a block owns
+// rows_blk (x, y) rows of one entry, partials = nblocks doubles of scratch,
+// out = R doubles
+int fdtd_energy_eval_f32(const void* tab, int n, int nblocks, int rows_blk, int R, void* partials, void* out, void* s);
+int fdtd_energy_eval_f64(const void* tab, int n, int nblocks, int rows_blk, int R, void* partials, void* out, void* s);
+int fdtd_energy_ent_size();
 }

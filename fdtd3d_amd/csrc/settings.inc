@@ -163,5 +163,14 @@ FDTD_INT (fluxSizeY, "--flux-sizey", 0, "Distance (cells) of the flux box from b
 FDTD_INT (fluxSizeZ, "--flux-sizez", 0, "Distance (cells) of the flux box from both z borders")
 FDTD_ACTION ("--same-size-flux", "Copy the x flux box distance to y and z")
 FDTD_INT (fluxReportStep, "--flux-report-step", 0, "Steps between flux reports; 0 = only at the end of the run")
+/* ---- extensions: field-energy monitor and decay-based stop (models/energy.py; Python driver) ---- */
+FDTD_BOOL (doUseEnergy, "--use-energy", "Monitor the vacuum-weighted field energy (1/2 eps0 E^2 + 1/2 mu0 H^2) in a box: a time series in the --json line, one line per sample with --log-level >= 1")
+FDTD_INT (energySizeX, "--energy-sizex", 0, "Distance (cells) of the energy box from both x borders (0 = the whole grid)")
+FDTD_INT (energySizeY, "--energy-sizey", 0, "Distance (cells) of the energy box from both y borders")
+FDTD_INT (energySizeZ, "--energy-sizez", 0, "Distance (cells) of the energy box from both z borders")
+FDTD_ACTION ("--same-size-energy", "Copy the x energy box distance to y and z")
+FDTD_INT (energyStep, "--energy-step", 0, "Steps between energy samples; 0 = automatic (a multiple of the blocked pass length or of the DFT / flux sampling step, at least 50)")
+FDTD_INT (energyStart, "--energy-start", 0, "First step at which the energy monitor samples")
+FDTD_FLOAT (stopDecayBy, "--stop-decay-by", 0.0, "Stop the run once the source has ended and the field energy in the box has fallen to this fraction of its peak (--time-steps stays the upper bound; pulsed sources only); 0 = off; implies --use-energy")
 FDTD_BOOL (doPrintJson, "--json", "Print a JSON summary line after the run")
 FDTD_INT (warmupSteps, "--warmup-steps", 0, "Untimed time steps run before the timed loop (benchmarking; they advance the simulation)")

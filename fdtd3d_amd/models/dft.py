@@ -94,11 +94,25 @@ def monitor_box_requests(scheme, margin: Sequence[int]) -> List[Request]:
 def refuse_config(cfg, checkpoints: bool = False) -> Optional[str]:
     """Why the configuration cannot run with its DFT monitors (None: it can).
     Never a silent fallback."""
-    if not (cfg.use_dft or cfg.ntff_dft or cfg.use_flux):
+    energy = cfg.use_energy or cfg.stop_decay_by > 0
+    if not (cfg.use_dft or cfg.ntff_dft or cfg.use_flux or energy):
         return None
     flag = "--use-dft" if cfg.use_dft else "--ntff-dft" if cfg.ntff_dft else ""
     if cfg.use_flux:
         flag = flag + " / --use-flux" if flag else "--use-flux"
+    if energy and not flag:
+        # the energy monitor alone (models/energy.py): the same refusals in its own words
+        flag = "--stop-decay-by" if cfg.stop_decay_by > 0 and not cfg.use_energy else "--use-energy"
+        if cfg.complex_values:
+            return "%s with --complex-field-values: the energy monitor needs a real-valued run" % flag
+        if cfg.use_amp_mode:
+            return "%s with --use-amp-mode: the energy monitor does not follow the amplitude steps" % flag
+        if checkpoints:
+            return ("%s with --checkpoint-dir / --load-from-file: the energy series and its peak are not part of a "
+                    "checkpoint" % flag)
+        return None
+    if energy:
+        flag += " / --use-energy"
     if cfg.complex_values:
         return ("%s with --complex-field-values: a complex run already carries the phasor; the monitor needs a "
                 "real-valued run" % flag)

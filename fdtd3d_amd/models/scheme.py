@@ -126,6 +126,11 @@ class SchemeConfig:
     use_flux: bool = False                   # Poynting flux through a closed box from DFT phasors (models/flux.py)
     flux_size: Tuple[int, int, int] = (0, 0, 0)  # distance of the flux box from the borders
     flux_report_step: int = 0                # steps between flux reports; 0 = only at the end
+    use_energy: bool = False                 # field-energy monitor on a box (models/energy.py)
+    energy_size: Tuple[int, int, int] = (0, 0, 0)  # distance of the energy box from the borders (0 = whole grid)
+    energy_step: int = 0                     # steps between samples; 0 = automatic (models/energy.py auto_step)
+    energy_start: int = 0
+    stop_decay_by: float = 0.0               # stop once the energy is this fraction of its peak; 0 = off
 
     @classmethod
     def from_settings(cls, s) -> "SchemeConfig":
@@ -161,7 +166,9 @@ class SchemeConfig:
             use_dft=s.doUseDft, dft_wavelengths=s.dftWavelengths, dft_step=s.dftStep, dft_start=s.dftStart,
             dft_size=(s.dftSizeX, s.dftSizeY, s.dftSizeZ), dft_h_time=s.dftHTime, ntff_dft=s.doUseNtffDft,
             use_flux=s.doUseFlux, flux_size=(s.fluxSizeX, s.fluxSizeY, s.fluxSizeZ),
-            flux_report_step=s.fluxReportStep)
+            flux_report_step=s.fluxReportStep,
+            use_energy=s.doUseEnergy or s.stopDecayBy > 0, energy_size=(s.energySizeX, s.energySizeY, s.energySizeZ),
+            energy_step=s.energyStep, energy_start=s.energyStart, stop_decay_by=s.stopDecayBy)
 
 
 def _drude_coefs(dt: float, e0: float, eps, w, g, q: float):
@@ -230,6 +237,7 @@ class YeeScheme(BlockedStepping):
         # period == 0.  Unlike per-step hooks these keep the blocked / hybrid
         # passes: advance() ends a pass at every firing step.
         self.periodic: List[Tuple[int, int, Callable[["YeeScheme", int], None]]] = []
+        self.stop_requested: Optional[Tuple[int, str]] = None  # (step, reason) of request_stop()
         self.initialized = False
         from ..utils.profiler import PhaseProfiler
         self.prof = PhaseProfiler(self.device, cfg.profile_phases)
@@ -1655,9 +1663,20 @@ class YeeScheme(BlockedStepping):
             nxt = min(nxt, t)
         return nxt
 
+    def request_stop(self, reason: str) -> None:
+        """Periodic work asks ``advance()`` to return once the periodic work
+        of the current step has run (models/energy.py: the fields have
+        decayed).  On decomposed runs every rank must ask at the same step."""
+        self.stop_requested = (self.t, str(reason))
+
     def advance(self, n: int) -> None:
         """``n`` leapfrog steps; blocked / hybrid passes end at every step at
-        which periodic work fires, which then runs between passes."""
+        which periodic work fires, which then runs between passes.  Returns
+        early, after all the periodic work of a step, when some of it called
+        :meth:`request_stop`.  The request holds for this call only: a later
+        call steps on, and periodic work that still wants to stop asks again
+        at its next event."""
+        self.stop_requested = None
         end = self.t + n
         while self.t < end:
             nxt = self._next_periodic(self.t, end) if self.periodic else end
@@ -1665,6 +1684,8 @@ class YeeScheme(BlockedStepping):
             for period, off, fn in self.periodic:
                 if (self.t - off) % period == 0:
                     fn(self, self.t)
+                    if self.stop_requested is not None:
+                        end = self.t
 
     def _advance(self, n: int) -> None:
         """``n`` leapfrog steps, ``self.tb`` at a time through the temporally

@@ -818,6 +818,115 @@ class HipOps:
         self.launches += 2 if nblocks else 1
         return out
 
+    # -------------------------------------------------------- energy monitors
+    ENERGY_GROUPS_PER_BLOCK = 8192  # 16-byte groups a block walks at most (32 per thread)
+    ENERGY_MIN_BLOCKS = 2048        # small boxes: fewer rows per block until the launch has this many blocks
+    ENERGY_MERGE_MAX = 1 << 16      # longest row (elements) made by folding y into z
+    ENERGY_MAX_TABLES = 4           # cached device tables per monitor (the F / F_alt ping-pong needs 2)
+
+    def _energy_table(self, entries):
+        """(device table, entries, blocks, rows per block, partials) of a
+        monitor's non-empty entries with their current field arrays, or None
+        where every box is empty; every box checked against its array."""
+        import numpy as np
+        from .dft import vec_width
+        from .energy import ENERGY_ENT_SIZE
+        if entries.R < 1:
+            raise HipError("field_sumsq: at least one result row")
+        if int(self.lib.fdtd_energy_ent_size()) != ENERGY_ENT_SIZE:
+            raise HipError("EnergyEnt layout mismatch")
+        v = vec_width(self.dtype)
+        item = 16 // v
+        rows = []
+
+        def index(dev):
+            return torch.cuda.current_device() if dev.index is None else dev.index
+
+        for e in entries:
+            t = e.field
+            if t.device.type != "cuda" or index(t.device) != index(self.device):
+                raise HipError("field_sumsq: tensor on %s, backend on %s" % (t.device, self.device))
+            if t.dtype != self.dtype:
+                raise HipError("field_sumsq: tensor of %s, backend of %s" % (t.dtype, self.dtype))
+            if t.dim() != 3:
+                raise HipError("field_sumsq: 3D field arrays")
+            if not 0 <= e.row < entries.R:
+                raise HipError("field_sumsq: row %d of %d" % (e.row, entries.R))
+            lo, hi = e.box
+            for d in range(3):
+                if lo[d] < 0 or hi[d] > t.shape[d]:
+                    raise HipError("field_sumsq: box %s outside array %s" % (e.box, tuple(t.shape)))
+            if e.empty:
+                continue
+            sx, sy, sz = t.stride()
+            if (sz != 1 and t.shape[2] > 1) or sx < 0 or sy < 0:
+                raise HipError("field_sumsq: unit z stride and non-negative strides, got %s" % (t.stride(),))
+            if t.data_ptr() % item:
+                raise HipError("field_sumsq: field array not aligned to its element size")
+            lo, ext = list(lo), [hi[d] - lo[d] for d in range(3)]
+            # a box over whole short z rows of a row-contiguous array: fold y into z (2D / 1D layouts keep z = 1)
+            if lo[2] == 0 and ext[2] == t.shape[2] and sy == t.shape[2] and ext[1] * ext[2] <= self.ENERGY_MERGE_MAX:
+                lo, ext, sy = [lo[0], 0, lo[1] * sy], [ext[0], 1, ext[1] * ext[2]], 0
+            if max(sx, sy) >= 2 ** 31 or ext[0] * ext[1] >= 2 ** 31 or lo[2] + ext[2] >= 2 ** 31 - 16:
+                raise HipError("field_sumsq: stride or extent overflows int32 (%s, %s)" % (t.stride(), e.box))
+            z0, z1 = lo[2] & ~(v - 1), -(-(lo[2] + ext[2]) // v) * v
+            # vector loads read the aligned groups [z0, z1) of every row: every row start 16-byte aligned, and the
+            # last group of the last row inside the allocation
+            last = (lo[0] + ext[0] - 1) * sx + (lo[1] + ext[1] - 1) * sy + z1
+            room = t.untyped_storage().nbytes() // item - t.storage_offset()
+            vec = t.data_ptr() % 16 == 0 and sx % v == 0 and sy % v == 0 and last <= room
+            rows.append((e, lo, ext, sx, sy, (z1 - z0) // v, 1 if vec else 0))
+        if not rows:
+            return None
+        zg = max(r[5] for r in rows)
+        total = sum(r[2][0] * r[2][1] for r in rows)
+        rows_blk = max(1, min(self.ENERGY_GROUPS_PER_BLOCK // zg, total // self.ENERGY_MIN_BLOCKS))
+        e64 = np.zeros((len(rows), ENERGY_ENT_SIZE // 8), dtype=np.int64)
+        e32 = e64.view(np.int32)
+        blk = 0
+        for r, (e, lo, ext, sx, sy, g, vec) in enumerate(rows):
+            nb = -(-(ext[0] * ext[1]) // rows_blk)
+            if rows_blk * g >= 2 ** 31 - 4 * 256 or blk + nb >= 2 ** 31:
+                raise HipError("field_sumsq: too many blocks for one launch")
+            e64[r, 0] = e.field.data_ptr()
+            e32[r, 2], e32[r, 3] = sx, sy
+            e32[r, 4:7] = lo
+            e32[r, 7:10] = ext
+            e32[r, 10], e32[r, 11], e32[r, 12], e32[r, 13] = e.row, blk, nb, vec
+            blk += nb
+        table = torch.from_numpy(e64).to(self.device)
+        partials = torch.empty((blk,), dtype=torch.float64, device=self.device)
+        return (table, len(rows), blk, rows_blk, partials)
+
+    def field_sumsq(self, entries) -> torch.Tensor:
+        """(R,) float64 on the device: per entry the sum over its box of the
+        squares of the field, every element converted to fp64 first, added to
+        the entry's row (ops/energy.py ``EnergyEntries``) -- one launch over
+        every entry plus one that folds the blocks' partial sums per row in a
+        fixed order (energy_kernels.hip; no atomics, so the same input gives
+        the same bits).  Everything is validated before the first launch.  The
+        device table is cached on ``entries`` per set of field arrays (F /
+        F_alt ping-pong: the current arrays are looked up at every call)."""
+        key = tuple((e.field.data_ptr(), tuple(e.field.shape), tuple(e.field.stride()), e.field.dtype,
+                     e.field.device, e.field.storage_offset(), e.field.untyped_storage().nbytes(), e.box, e.row)
+                    for e in entries)
+        tab = entries.tables.get(key, False)
+        if tab is False:
+            tab = self._energy_table(entries)
+            if len(entries.tables) >= self.ENERGY_MAX_TABLES:
+                entries.tables.clear()  # reallocated field arrays: drop the tables (and partials) of the old ones
+            entries.tables[key] = tab
+        out = torch.empty((entries.R,), dtype=torch.float64, device=self.device)
+        if tab is None:
+            table, n, nblocks, rows_blk, partials = None, 0, 0, 1, None
+        else:
+            table, n, nblocks, rows_blk, partials = tab
+        rc = self.fn("energy_eval")(_ptr(table), c_int(n), c_int(nblocks), c_int(rows_blk), c_int(entries.R),
+                                    _ptr(partials), _ptr(out), _stream())
+        _check(rc, "energy_eval")
+        self.launches += 2 if nblocks else 1
+        return out
+
     def unpack(self, tensors: Sequence[torch.Tensor], box: Box, buf: torch.Tensor) -> None:
         shape = tuple(tensors[0].shape)
         n = 1

@@ -611,6 +611,21 @@ class TorchOps:
             out[t.face] += t.sign * (e[:, 0] * h[:, 0] + e[:, 1] * h[:, 1]).sum(dim=(1, 2, 3))
         return out
 
+    def field_sumsq(self, entries) -> torch.Tensor:
+        """(R,) float64: per entry the sum over its box of the squares of the
+        field, converted to fp64 first, added to the entry's row (ops/energy.py
+        ``EnergyEntries``).  The oracle of csrc/energy_kernels.hip."""
+        dev = entries.rows[0].field.device if len(entries) else "cpu"
+        out = torch.zeros((entries.R,), dtype=torch.float64, device=dev)
+        for e in entries:
+            if e.empty:
+                continue
+            (x0, y0, z0), (x1, y1, z1) = e.box
+            if e.field.dim() != 3 or min(x0, y0, z0) < 0 or any(e.box[1][d] > e.field.shape[d] for d in range(3)):
+                raise ValueError("field_sumsq: box %s outside array %s" % (e.box, tuple(e.field.shape)))
+            out[e.row] += e.field[x0:x1, y0:y1, z0:z1].double().square().sum()
+        return out
+
 
 class TfsfTable:
     """Per-component TF/SF correction list: ``target[off] += coef *

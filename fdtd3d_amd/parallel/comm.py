@@ -114,6 +114,14 @@ class DistComm:
         dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX, group=self.group)
         return float(t.item())
 
+    def allreduce_vec(self, values, op: str = "sum") -> List[float]:
+        """Elementwise all-reduce of a list of floats in fp64, one collective."""
+        dev = "cuda" if self.backend == "nccl" else "cpu"
+        t = torch.tensor([float(v) for v in values], dtype=torch.float64, device=dev)
+        if t.numel():
+            dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX, group=self.group)
+        return t.tolist()
+
 
 class LocalHub:
     """Mailboxes shared by ``world`` in-process ranks.  ``tagless``: one FIFO
@@ -197,5 +205,15 @@ class LocalComm:
         self.hub._red[self.rank] = float(v)
         self.hub._barrier.wait()
         r = sum(self.hub._red) if op == "sum" else max(self.hub._red)
+        self.hub._barrier.wait()
+        return r
+
+    def allreduce_vec(self, values, op: str = "sum") -> List[float]:
+        """Elementwise all-reduce of a list of floats, added in rank order:
+        every rank gets the same bits."""
+        self.hub._red[self.rank] = [float(v) for v in values]
+        self.hub._barrier.wait()
+        f = sum if op == "sum" else max
+        r = [f(col) for col in zip(*self.hub._red)]
         self.hub._barrier.wait()
         return r

@@ -464,6 +464,14 @@ class HaloExchanger:
     def allreduce_max(self, v: float) -> float:
         return float(self.comm.allreduce(v, "max"))
 
+    def allreduce_fsum(self, values: Sequence[float]) -> List[float]:
+        """Elementwise fp64 sum of a list of floats over the ranks (one
+        collective where the transport has ``allreduce_vec``)."""
+        vec = getattr(self.comm, "allreduce_vec", None)
+        if vec is not None:
+            return [float(v) for v in vec(values, "sum")]
+        return [float(self.comm.allreduce(float(v), "sum")) for v in values]
+
 
 def _tag(kind: str, axis: int) -> int:
     return (0 if kind == "H" else 10) + axis

@@ -163,12 +163,15 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
     if status != EXIT_OK:
         return status
     log.set_level(settings.logLevel)
-    if settings.doUseDft or settings.doUseNtffDft or settings.doUseFlux:
-        # refused before anything is set up, never a silent fallback (models/dft.py)
+    if (settings.doUseDft or settings.doUseNtffDft or settings.doUseFlux or settings.doUseEnergy
+            or settings.stopDecayBy != 0):
+        # refused before anything is set up, never a silent fallback (models/dft.py, models/energy.py)
         from .models.dft import refuse_config
+        from .models.energy import refuse_energy_config
         from .models.scheme import SchemeConfig
-        why = refuse_config(SchemeConfig.from_settings(settings),
-                            checkpoints=bool(settings.checkpointDir or settings.loadFromFile))
+        cfg0 = SchemeConfig.from_settings(settings)
+        ckpt = bool(settings.checkpointDir or settings.loadFromFile)
+        why = refuse_config(cfg0, checkpoints=ckpt) or refuse_energy_config(cfg0, checkpoints=ckpt)
         if why:
             out.write("ERROR: %s\n" % why)
             return EXIT_ERROR
@@ -234,6 +237,23 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         flux_reported = [None, None]  # (step, result) of the last periodic report
         if scheme.cfg.flux_report_step > 0:
             scheme.add_periodic(scheme.cfg.flux_report_step, 0, flux_hook)
+    energy = None
+    if scheme.cfg.use_energy:
+        from .models.energy import energy_from_config
+        from .utils.assertions import FdtdError
+        try:
+            # after the DFT / flux monitors: the automatic step follows theirs (models/energy.py)
+            energy = energy_from_config(scheme)
+        except FdtdError as e:
+            out.write("ERROR: %s\n" % e)
+            if dist is not None:
+                dist.destroy_process_group()
+            return EXIT_ERROR
+        energy_out = out if rank == 0 else open(os.devnull, "w")  # one sink for every energy line
+        if settings.logLevel >= 1:
+            # one line per sample (reads that sample alone to the host)
+            scheme.add_periodic(energy.step, energy.start % energy.step,
+                                lambda s, t: energy.report_sample(energy_out) if t >= energy.start else None)
     steps = max(0, settings.numTimeSteps - start_step)
 
     def sync():
@@ -244,8 +264,9 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
 
     warm = min(max(0, settings.warmupSteps), steps)
     if warm:
+        t_warm = scheme.t
         scheme.advance(warm)  # regular steps only: amplitude mode follows the timed ones
-        steps -= warm
+        steps -= scheme.t - t_warm  # (the energy monitor may have ended the warm-up early)
     sync()
     scheme.prof.reset()  # phase timings cover the timed steps only
     if halo is not None:
@@ -277,6 +298,17 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         flux_result = flux_reported[1]  # the last step's periodic report is the final one
     elif flux is not None:
         flux_result = flux.report(scheme.t, out if rank == 0 else open(os.devnull, "w"))
+    energy_result = None
+    if energy is not None:
+        # every rank: the series is summed over the ranks
+        energy_result = energy.report(scheme.t, energy_out)
+        if rank == 0 and energy.stopped_at is not None:
+            out.write("=== stopped at step %d: field energy %.6g of its peak (--stop-decay-by %g)\n"
+                      % (energy.stopped_at, energy_result["ratio"], energy.decay_by))
+        elif rank == 0 and energy.decay_by > 0:
+            out.write("WARNING: --stop-decay-by %g not reached within --time-steps %d: field energy %.6g of its peak "
+                      "at step %d (a static residue or the absorber's reflection can floor the decay)\n"
+                      % (energy.decay_by, settings.numTimeSteps, energy_result["ratio"], scheme.t))
     if settings.checkpointDir:
         save_checkpoint(scheme, settings.checkpointDir)
     phases = scheme.prof.summary() if scheme.prof.enabled else None
@@ -306,6 +338,8 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                     rec["dft"]["ntff"] = monitors["ntff"].info()
             if flux_result is not None:
                 rec["flux"] = flux.info(flux_result)
+            if energy_result is not None:
+                rec["energy"] = energy.info(energy_result)
             if breakdown is not None:
                 rec["rank0_passes"] = breakdown  # decomposed passes: interior / exchange wait / shell ms
             if scheme.device.type == "cuda":
