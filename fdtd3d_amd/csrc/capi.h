@@ -214,6 +214,18 @@ int fdtd_flux_eval_f64(const void* tab, int n, int nblocks, int K, const void* f
                        void* s);
 int fdtd_flux_ent_size();
 
+// radiation vectors of the currents on box faces from DFT accumulators
+// (farfield_kernels.hip): tab = n device entries of fdtd_farfield_ent_size()
+// bytes (face groups), dirs = A x 3 device doubles, wn = K device doubles,
+// fold = device ints (7 slot starts, then (partials row, current, sign)),
+// partials = rows x K x 4 x A x 2 doubles of scratch, out = K x A x 6 x 2
+// doubles
+int fdtd_farfield_eval_f32(const void* tab, int n, int nblocks, int K, int A, const void* dirs, const void* wn,
+                           double dx, const void* fold, void* partials, void* out, void* s);
+int fdtd_farfield_eval_f64(const void* tab, int n, int nblocks, int K, int A, const void* dirs, const void* wn,
+                           double dx, const void* fold, void* partials, void* out, void* s);
+int fdtd_farfield_ent_size();
+
 // sums of squares over boxes of field arrays (energy_kernels.hip): tab = n
 // device entries of fdtd_energy_ent_size() bytes ordered by blk0, a block owns
 // rows_blk (x, y) rows of one entry, partials = nblocks doubles of scratch,

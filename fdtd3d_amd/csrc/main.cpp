@@ -101,7 +101,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr,
                  "fdtd3d (native): decomposed 3D CPML outside whole 4-cell z rows, PML / TF/SF in 1D, TF/SF boxes reaching "
                  "the UPML, metamaterials outside the 3D drude-sphere scene, amplitude mode with NTFF, parallel "
-                 "grids with NTFF in 2D, checkpoints beyond plain media, running-DFT and flux monitors (--use-dft, --ntff-dft, --use-flux), "
+                 "grids with NTFF in 2D, checkpoints beyond plain media, running-DFT, flux and far-field monitors (--use-dft, --ntff-dft, --use-flux, --use-farfield), "
                  "the energy monitor and its decay-based stop (--use-energy, --stop-decay-by), "
                  "and complex fields with amplitude mode, "
                  "NTFF, checkpoints or parallel grids run through the Python driver: python -m fdtd3d_amd <same options>\n");

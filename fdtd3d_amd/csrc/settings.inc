@@ -163,6 +163,14 @@ FDTD_INT (fluxSizeY, "--flux-sizey", 0, "Distance (cells) of the flux box from b
 FDTD_INT (fluxSizeZ, "--flux-sizez", 0, "Distance (cells) of the flux box from both z borders")
 FDTD_ACTION ("--same-size-flux", "Copy the x flux box distance to y and z")
 FDTD_INT (fluxReportStep, "--flux-report-step", 0, "Steps between flux reports; 0 = only at the end of the run")
+/* ---- extensions: far-field monitor on the NTFF surface (models/farfield.py; Python driver) ---- */
+FDTD_BOOL (doUseFarfield, "--use-farfield", "Monitor the far field of the currents on a closed box from running-DFT phasors (3D; wavelengths, step and start from --dft-wavelengths, --dft-step, --dft-start): radiant intensity, total radiated power, directivity and, with TF/SF, the bistatic RCS per wavelength")
+FDTD_INT (farfieldSizeX, "--farfield-sizex", 0, "Distance (cells) of the far-field box from both x borders (0 = the --ntff-size* value)")
+FDTD_INT (farfieldSizeY, "--farfield-sizey", 0, "Distance (cells) of the far-field box from both y borders")
+FDTD_INT (farfieldSizeZ, "--farfield-sizez", 0, "Distance (cells) of the far-field box from both z borders")
+FDTD_ACTION ("--same-size-farfield", "Copy the x far-field box distance to y and z")
+FDTD_INT (farfieldNTheta, "--farfield-ntheta", 37, "Polar angles of the far-field report grid, uniform over [0, pi] with both ends")
+FDTD_INT (farfieldNPhi, "--farfield-nphi", 72, "Azimuthal angles of the far-field report grid, uniform over [0, 2 pi)")
 /* ---- extensions: field-energy monitor and decay-based stop (models/energy.py; Python driver) ---- */
 FDTD_BOOL (doUseEnergy, "--use-energy", "Monitor the vacuum-weighted field energy (1/2 eps0 E^2 + 1/2 mu0 H^2) in a box: a time series in the --json line, one line per sample with --log-level >= 1")
 FDTD_INT (energySizeX, "--energy-sizex", 0, "Distance (cells) of the energy box from both x borders (0 = the whole grid)")

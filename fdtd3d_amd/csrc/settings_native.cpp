@@ -117,6 +117,8 @@ SettingsStatus Settings::parse(const std::vector<std::string>& t, bool is_cmd) {
       dftSizeY = dftSizeZ = dftSizeX;
     } else if (a == "--same-size-flux") {
       fluxSizeY = fluxSizeZ = fluxSizeX;
+    } else if (a == "--same-size-farfield") {
+      farfieldSizeY = farfieldSizeZ = farfieldSizeX;
     } else if (a == "--same-size-energy") {
       energySizeY = energySizeZ = energySizeX;
     } else if (a == "--same-size-topology") {

@@ -230,3 +230,23 @@ def dump_materials(scheme, settings, directory: Optional[str] = None) -> List[st
                 else:
                     files += d.dump_grid(g, None, dim=dim)
     return files
+
+
+def dump_farfield(result, wavelengths, step: int, directory: str) -> List[str]:
+    """The far-field pattern of a monitor (models/farfield.py ``evaluate``) as
+    one text table per wavelength, ``farfield<k>_[timestep=<step>].txt``: a
+    header line, then one row ``theta phi U directivity [rcs]`` per direction
+    of the report grid (radians, W / sr, m^2)."""
+    import os
+    files: List[str] = []
+    th, ph = result["thetas"].tolist(), result["phis"].tolist()
+    for k, wl in enumerate(wavelengths):
+        cols = [result["U"][k], result["directivity"][k]] + ([result["rcs"][k]] if "rcs" in result else [])
+        path = os.path.join(directory, "farfield%d_[timestep=%d].txt" % (k, step))
+        with open(path, "w") as f:
+            f.write("# wavelength %.17g: theta phi U directivity%s\n" % (wl, " rcs" if "rcs" in result else ""))
+            for i, t in enumerate(th):
+                for j, p in enumerate(ph):
+                    f.write("%.17g %.17g %s\n" % (t, p, " ".join("%.17g" % float(c[i, j]) for c in cols)))
+        files.append(path)
+    return files

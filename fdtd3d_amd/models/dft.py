@@ -95,11 +95,13 @@ def refuse_config(cfg, checkpoints: bool = False) -> Optional[str]:
     """Why the configuration cannot run with its DFT monitors (None: it can).
     Never a silent fallback."""
     energy = cfg.use_energy or cfg.stop_decay_by > 0
-    if not (cfg.use_dft or cfg.ntff_dft or cfg.use_flux or energy):
+    if not (cfg.use_dft or cfg.ntff_dft or cfg.use_flux or cfg.use_farfield or energy):
         return None
     flag = "--use-dft" if cfg.use_dft else "--ntff-dft" if cfg.ntff_dft else ""
     if cfg.use_flux:
         flag = flag + " / --use-flux" if flag else "--use-flux"
+    if cfg.use_farfield:
+        flag = flag + " / --use-farfield" if flag else "--use-farfield"
     if energy and not flag:
         # the energy monitor alone (models/energy.py): the same refusals in its own words
         flag = "--stop-decay-by" if cfg.stop_decay_by > 0 and not cfg.use_energy else "--use-energy"
@@ -125,6 +127,8 @@ def refuse_config(cfg, checkpoints: bool = False) -> Optional[str]:
         return "--ntff-dft needs --use-ntff on a 3D run"
     if cfg.use_flux and cfg.scheme != "3d":
         return "--use-flux needs a 3D run"
+    if cfg.use_farfield and cfg.scheme != "3d":
+        return "--use-farfield needs a 3D run"
     return None
 
 

@@ -72,10 +72,11 @@ def auto_step(scheme) -> int:
     """The smallest multiple of the run's pass length -- with a DFT or flux
     monitor registered: of its sampling step -- that is at least
     ``AUTO_MIN_STEP`` steps."""
+    from .farfield import FarFieldMonitor
     from .flux import FluxMonitor
     base = pass_length(scheme)
     steps = [int(fn.__self__.step) for _, _, fn in scheme.periodic
-             if isinstance(getattr(fn, "__self__", None), (DftMonitor, FluxMonitor))]
+             if isinstance(getattr(fn, "__self__", None), (DftMonitor, FluxMonitor, FarFieldMonitor))]
     if steps:
         base = 1
         for s in steps:

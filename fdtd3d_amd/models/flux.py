@@ -62,6 +62,27 @@ def flux_from_config(scheme) -> Optional["FluxMonitor"]:
                        cfg.dft_step, cfg.dft_start)
 
 
+def slab_operand(dft: DftMonitor, scheme, comp: str, plan, gathered: bool) -> Optional[FluxOperand]:
+    """The accumulators of (comp, the plan's box) of ``dft`` in the padded
+    layout of a serial monitor, with the plan's first sample and averaging
+    axes; ``gathered``: collected from the ranks on rank 0 (None elsewhere).
+    Shared with models/farfield.py."""
+    box = _plan_box(plan)
+    i = dft.index((comp, box))
+    avg = [len(offs) == 2 for _, _, offs in plan]
+    if not gathered:
+        e = dft.entries.rows[i]
+        return FluxOperand(e.acc, (0, 0, e.box[0][2] - z_pad(e.box, vec_width(e.acc.dtype))[0]), avg)
+    raw = dft.gather_accumulators(scheme, i)
+    if raw is None:
+        return None
+    v = vec_width(raw.dtype)
+    z0 = z_pad(box, v)[0]
+    acc = torch.zeros(acc_shape(box, raw.shape[0], v), dtype=raw.dtype, device=raw.device)
+    acc[..., box[0][2] - z0:box[1][2] - z0] = raw
+    return FluxOperand(acc, (0, 0, box[0][2] - z0), avg)
+
+
 class FluxMonitor:
     """Power through the box ``margin`` cells inside the grid borders at
     ``wavelengths``; ``step`` (0 = automatic, passes between samples stay
@@ -132,20 +153,7 @@ class FluxMonitor:
     def _operand(self, comp: str, plan, gathered: bool) -> Optional[FluxOperand]:
         """The accumulators of (comp, the plan's box) in the padded layout of a
         serial monitor, with the plan's first sample and averaging axes."""
-        box = _plan_box(plan)
-        i = self.dft.index((comp, box))
-        avg = [len(offs) == 2 for _, _, offs in plan]
-        if not gathered:
-            e = self.dft.entries.rows[i]
-            return FluxOperand(e.acc, (0, 0, e.box[0][2] - z_pad(e.box, vec_width(e.acc.dtype))[0]), avg)
-        raw = self.dft.gather_accumulators(self.scheme, i)
-        if raw is None:
-            return None
-        v = vec_width(raw.dtype)
-        z0 = z_pad(box, v)[0]
-        acc = torch.zeros(acc_shape(box, raw.shape[0], v), dtype=raw.dtype, device=raw.device)
-        acc[..., box[0][2] - z0:box[1][2] - z0] = raw
-        return FluxOperand(acc, (0, 0, box[0][2] - z0), avg)
+        return slab_operand(self.dft, self.scheme, comp, plan, gathered)
 
     def _build_terms(self, gathered: bool) -> Optional[FluxTerms]:
         terms = FluxTerms(len(self.wavelengths), len(self.faces))

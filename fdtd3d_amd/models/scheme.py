@@ -126,6 +126,10 @@ class SchemeConfig:
     use_flux: bool = False                   # Poynting flux through a closed box from DFT phasors (models/flux.py)
     flux_size: Tuple[int, int, int] = (0, 0, 0)  # distance of the flux box from the borders
     flux_report_step: int = 0                # steps between flux reports; 0 = only at the end
+    use_farfield: bool = False               # far-field monitor on a closed box (models/farfield.py)
+    farfield_size: Tuple[int, int, int] = (0, 0, 0)  # distance of the far-field box from the borders
+    farfield_ntheta: int = 37                # report grid: polar angles over [0, pi], both ends
+    farfield_nphi: int = 72                  # report grid: azimuthal angles over [0, 2 pi)
     use_energy: bool = False                 # field-energy monitor on a box (models/energy.py)
     energy_size: Tuple[int, int, int] = (0, 0, 0)  # distance of the energy box from the borders (0 = whole grid)
     energy_step: int = 0                     # steps between samples; 0 = automatic (models/energy.py auto_step)
@@ -167,6 +171,10 @@ class SchemeConfig:
             dft_size=(s.dftSizeX, s.dftSizeY, s.dftSizeZ), dft_h_time=s.dftHTime, ntff_dft=s.doUseNtffDft,
             use_flux=s.doUseFlux, flux_size=(s.fluxSizeX, s.fluxSizeY, s.fluxSizeZ),
             flux_report_step=s.fluxReportStep,
+            use_farfield=s.doUseFarfield,
+            farfield_size=tuple(f if f > 0 else n for f, n in zip(
+                (s.farfieldSizeX, s.farfieldSizeY, s.farfieldSizeZ), (s.ntffSizeX, s.ntffSizeY, s.ntffSizeZ))),
+            farfield_ntheta=s.farfieldNTheta, farfield_nphi=s.farfieldNPhi,
             use_energy=s.doUseEnergy or s.stopDecayBy > 0, energy_size=(s.energySizeX, s.energySizeY, s.energySizeZ),
             energy_step=s.energyStep, energy_start=s.energyStart, stop_decay_by=s.stopDecayBy)
 

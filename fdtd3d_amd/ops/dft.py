@@ -10,7 +10,10 @@ dft_kernels.hip).  The padded cells are never written and stay zero.
 
 ``FluxTerms`` describe what ``dft_flux(terms)`` evaluates from such
 accumulators: products of face-centre averages summed over the faces of a box
-(models/flux.py; csrc/flux_kernels.hip).
+(models/flux.py; csrc/flux_kernels.hip).  ``FarTerms`` describe what
+``dft_farfield(terms, dirs, wavenumbers)`` evaluates from them: the radiation
+vectors of the equivalent currents on the faces (models/farfield.py; csrc/
+farfield_kernels.hip).
 """
 
 from __future__ import annotations
@@ -155,6 +158,60 @@ class FluxTerms:
     def add(self, term: FluxTerm) -> FluxTerm:
         if not 0 <= term.face < self.faces:
             raise ValueError("FluxTerms: face %d of %d" % (term.face, self.faces))
+        self.rows.append(term)
+        self.table = None
+        return term
+
+    def __iter__(self):
+        return iter(self.rows)
+
+    def __len__(self):
+        return len(self.rows)
+
+
+# ------------------------------------------------------------- far-field terms
+FAR_ENT_SIZE = 216   # bytes of a device table entry of ``dft_farfield`` (fdtd_farfield_ent_size)
+FAR_GROUP = 4        # terms of one face group: they share the cells and so the phase factors
+FAR_SLOTS = 6        # N_x, N_y, N_z, L_x, L_y, L_z
+
+
+class FarTerm:
+    """``sign * sum over the face cells c of avg(acc[k, 0] + i acc[k, 1])(c)
+    exp(-i kappa_k rhat . r'(c))`` added to component ``slot`` (0..5: ``N_x,
+    N_y, N_z, L_x, L_y, L_z``) of the radiation vectors; ``r'(c) = pos0 + dx *
+    (cell index)``, ``pos0`` the first face-cell centre in metres relative to
+    the phase origin, ``extent`` the face's cells per axis (1 along its
+    normal), ``operand`` a :class:`FluxOperand`."""
+    __slots__ = ("slot", "sign", "extent", "operand", "pos0")
+
+    def __init__(self, slot: int, sign: int, extent, operand: FluxOperand, pos0):
+        if sign not in (1, -1):
+            raise ValueError("FarTerm: sign +1 or -1")
+        if not 0 <= int(slot) < FAR_SLOTS:
+            raise ValueError("FarTerm: slot 0..%d" % (FAR_SLOTS - 1))
+        self.slot, self.sign = int(slot), int(sign)
+        self.extent = tuple(int(v) for v in extent)
+        self.operand = operand
+        self.pos0 = tuple(float(v) for v in pos0)
+        if len(self.extent) != 3 or len(self.pos0) != 3:
+            raise ValueError("FarTerm: extent and pos0 per axis")
+
+    @property
+    def empty(self) -> bool:
+        return any(v <= 0 for v in self.extent)
+
+
+class FarTerms:
+    """The currents of one far-field monitor (``ops.dft_farfield``) at ``k``
+    wavelengths on a grid of step ``dx`` and, on the HIP backend, its cached
+    device table."""
+
+    def __init__(self, k: int, dx: float):
+        self.k, self.dx = int(k), float(dx)
+        self.rows: List[FarTerm] = []
+        self.table = None
+
+    def add(self, term: FarTerm) -> FarTerm:
         self.rows.append(term)
         self.table = None
         return term

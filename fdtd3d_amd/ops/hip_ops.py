@@ -818,6 +818,124 @@ class HipOps:
         self.launches += 2 if nblocks else 1
         return out
 
+    # ----------------------------------------------------- far-field monitors
+    FAR_TARGET_BLOCKS = 1024  # few directions: a face's cells are split over blocks until the launch has this many
+    FAR_MAX_SPLITS = 8        # ... at most this many per face group: the partials stay (4 / 6) groups x 8 x `out`
+
+    def _far_table(self, terms, A: int):
+        """(device table, groups, blocks, fold table, partials) of a far-field
+        monitor's non-empty terms for ``A`` directions; every operand's reach
+        checked against its accumulator block.  Terms that share extent and
+        first cell form a group of up to 4 (one phase factor serves them), in
+        the order of their first term; the fold table keeps the terms' own
+        order per slot."""
+        import numpy as np
+        from .dft import DFT_MAX_K, FAR_ENT_SIZE, FAR_GROUP, FAR_SLOTS, vec_width
+        K = terms.k
+        if not 1 <= K <= DFT_MAX_K:
+            raise HipError("dft_farfield: 1..%d wavelengths, got %d" % (DFT_MAX_K, K))
+        if int(self.lib.fdtd_farfield_ent_size()) != FAR_ENT_SIZE:
+            raise HipError("FarEnt layout mismatch")
+        v = vec_width(self.dtype)
+        groups, where = [], {}  # [terms of the group]; (extent, pos0) -> the open group
+        member = []             # per non-empty term: (group, current)
+        for t in terms:
+            if t.empty:
+                continue
+            op = t.operand
+            self._check_tensor(op.acc)
+            why = op.reach_error(t.extent, K)
+            if why:
+                raise HipError("dft_farfield: " + why)
+            if op.acc.data_ptr() % 16:
+                raise HipError("dft_farfield: accumulators must be 16-byte aligned")
+            if op.acc[0, 0].numel() >= 2 ** 31 or t.extent[0] * t.extent[1] * t.extent[2] >= 2 ** 31 - 256:
+                raise HipError("dft_farfield: accumulator block or face too large")
+            key = (t.extent, t.pos0)
+            g = where.get(key)
+            if g is None or len(groups[g]) == FAR_GROUP:
+                g = where[key] = len(groups)
+                groups.append([])
+            member.append((t, g, len(groups[g])))
+            groups[g].append(t)
+        tiles = -(-A // 256)
+        per_group = K * tiles
+        want = -(-self.FAR_TARGET_BLOCKS // max(1, len(groups) * per_group))
+        e64 = np.zeros((max(1, len(groups)), FAR_ENT_SIZE // 8), dtype=np.int64)
+        e32, f64 = e64.view(np.int32), e64.view(np.float64)
+        blk, prow, prow0 = 0, 0, []
+        for r, grp in enumerate(groups):
+            ext = grp[0].extent
+            chunks = -(-(ext[0] * ext[1] * ext[2]) // 256)
+            splits = max(1, min(want, self.FAR_MAX_SPLITS, chunks))
+            if blk + splits * per_group >= 2 ** 31:
+                raise HipError("dft_farfield: too many directions for one launch")
+            f64[r, 8:11] = grp[0].pos0
+            for c, t in enumerate(grp):
+                op = t.operand
+                nx, ny, nz = op.acc.shape[2:]
+                e64[r, c] = op.acc.data_ptr()
+                e64[r, 4 + c] = nx * ny * nz
+                e32[r, 22 + c], e32[r, 26 + c] = ny * nz, nz
+                e32[r, 30 + 3 * c:33 + 3 * c] = op.first
+                # z-normal faces: a lane loads the aligned 16-byte group around its z samples
+                zvec = t.extent[2] == 1 and nz % v == 0
+                e32[r, 42 + c] = sum(1 << a for a in range(3) if op.avg[a]) | (8 if zvec else 0)
+            e32[r, 46:49] = ext
+            e32[r, 49], e32[r, 50], e32[r, 51], e32[r, 52] = len(grp), blk, splits, prow
+            prow0.append((prow, splits))
+            blk += splits * per_group
+            prow += splits
+        fold = [0] * (FAR_SLOTS + 1)
+        rows = []
+        for slot in range(FAR_SLOTS):
+            fold[slot] = len(rows) // 3
+            for t, g, c in member:
+                if t.slot == slot:
+                    for s in range(prow0[g][1]):
+                        rows += [prow0[g][0] + s, c, t.sign]
+        fold[FAR_SLOTS] = len(rows) // 3
+        if prow * K * FAR_GROUP * A * 2 >= 2 ** 40:
+            raise HipError("dft_farfield: too many directions for one call")
+        table = torch.from_numpy(e64).to(self.device)
+        fd = torch.tensor(fold + rows, dtype=torch.int32).to(self.device)
+        partials = torch.empty((max(1, prow), K, FAR_GROUP, A, 2), dtype=torch.float64, device=self.device)
+        return (table, len(groups), blk, fd, partials)
+
+    def dft_farfield(self, terms, dirs, wavenumbers) -> torch.Tensor:
+        """(K, A, 6, 2) float64 on the device: the radiation vectors ``N_x,
+        N_y, N_z, L_x, L_y, L_z`` (re, im) of ``terms`` (ops/dft.py
+        ``FarTerms``) in the directions ``dirs`` (A, 3) fp64 at
+        ``wavenumbers`` (K,) fp64, averaged and summed in fp64 from the raw
+        accumulators -- one launch over every face group, direction and
+        wavelength plus one that folds the partial sums per slot in a fixed
+        order (farfield_kernels.hip; no atomics, so the same input gives the
+        same bits).  The device table is cached on ``terms`` per direction
+        count (``FarTerms.add`` drops it)."""
+        dirs = torch.as_tensor(dirs)
+        wn = torch.as_tensor(wavenumbers)
+        if dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.dtype != torch.float64:
+            raise HipError("dft_farfield: dirs of shape (A, 3) in float64, got %s %s" % (tuple(dirs.shape), dirs.dtype))
+        if wn.dim() != 1 or wn.shape[0] != terms.k or wn.dtype != torch.float64:
+            raise HipError("dft_farfield: %d wavenumbers in float64, got %s %s" % (terms.k, tuple(wn.shape), wn.dtype))
+        A = int(dirs.shape[0])
+        if A >= 2 ** 24:
+            raise HipError("dft_farfield: at most 2^24 directions a call")
+        key = (A,) + tuple(t.operand.acc.data_ptr() for t in terms)
+        if terms.table is None or terms.table[0] != key:
+            terms.table = (key, self._far_table(terms, A))
+        table, n, nblocks, fold, partials = terms.table[1]
+        out = torch.empty((terms.k, A, 6, 2), dtype=torch.float64, device=self.device)
+        if A == 0:
+            return out
+        d = dirs.to(self.device).contiguous()
+        w = wn.to(self.device).contiguous()
+        rc = self.fn("farfield_eval")(_ptr(table), c_int(n), c_int(nblocks), c_int(terms.k), c_int(A), _ptr(d), _ptr(w),
+                                      c_double(terms.dx), _ptr(fold), _ptr(partials), _ptr(out), _stream())
+        _check(rc, "farfield_eval")
+        self.launches += 2 if nblocks else 1
+        return out
+
     # -------------------------------------------------------- energy monitors
     ENERGY_GROUPS_PER_BLOCK = 8192  # 16-byte groups a block walks at most (32 per thread)
     ENERGY_MIN_BLOCKS = 2048        # small boxes: fewer rows per block until the launch has this many blocks

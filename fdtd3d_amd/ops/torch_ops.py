@@ -611,6 +611,50 @@ class TorchOps:
             out[t.face] += t.sign * (e[:, 0] * h[:, 0] + e[:, 1] * h[:, 1]).sum(dim=(1, 2, 3))
         return out
 
+    def dft_farfield(self, terms, dirs, wavenumbers) -> torch.Tensor:
+        """(K, A, 6, 2) float64 (re, im): per term ``sign * sum over the face
+        cells c of avg(acc[k, 0] + i acc[k, 1])(c) exp(-i kappa_k rhat_a .
+        r'(c))`` added to its slot, ``r'(c) = pos0 + dx * (cell index)``
+        (ops/dft.py ``FarTerms``); ``dirs`` (A, 3) fp64 unit vectors,
+        ``wavenumbers`` (K,) fp64.  The face-centre average of the 1, 2 or 4
+        samples is taken in fp64 whatever the accumulators' precision, and
+        every (cell, direction) gets its own ``exp``: the definition, not a
+        factorisation.  The oracle of csrc/farfield_kernels.hip."""
+        dirs = torch.as_tensor(dirs)
+        wn = torch.as_tensor(wavenumbers)
+        if dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.dtype != torch.float64:
+            raise ValueError("dft_farfield: dirs of shape (A, 3) in float64, got %s %s" % (tuple(dirs.shape), dirs.dtype))
+        if wn.dim() != 1 or wn.shape[0] != terms.k or wn.dtype != torch.float64:
+            raise ValueError("dft_farfield: %d wavenumbers in float64, got %s %s" % (terms.k, tuple(wn.shape), wn.dtype))
+        dev = terms.rows[0].operand.acc.device if len(terms) else dirs.device
+        dirs, wn = dirs.to(dev), wn.to(dev)
+        out = torch.zeros((terms.k, dirs.shape[0], 6), dtype=torch.complex128, device=dev)
+        for t in terms:
+            if t.empty:
+                continue
+            why = t.operand.reach_error(t.extent, terms.k)
+            if why:
+                raise ValueError("dft_farfield: " + why)
+            op, acc, cnt = t.operand, None, 0
+            for ox in ((0, 1) if op.avg[0] else (0,)):
+                for oy in ((0, 1) if op.avg[1] else (0,)):
+                    for oz in ((0, 1) if op.avg[2] else (0,)):
+                        o = (ox, oy, oz)
+                        sl = tuple(slice(op.first[a] + o[a], op.first[a] + o[a] + t.extent[a]) for a in range(3))
+                        v = op.acc[(slice(None), slice(None)) + sl].to(torch.float64)
+                        acc = v if acc is None else acc + v
+                        cnt += 1
+            acc = acc / cnt
+            val = torch.complex(acc[:, 0], acc[:, 1]).reshape(terms.k, -1)          # (K, C)
+            pos = torch.stack(torch.meshgrid(*[t.pos0[a] + terms.dx * torch.arange(t.extent[a], dtype=torch.float64,
+                                                                                   device=dev) for a in range(3)],
+                                             indexing="ij"), dim=-1).reshape(-1, 3)  # (C, 3)
+            proj = pos @ dirs.transpose(0, 1)                                        # (C, A)
+            for k in range(terms.k):
+                ph = torch.exp(torch.complex(torch.zeros_like(proj), -wn[k] * proj))
+                out[k, :, t.slot] += t.sign * (val[k].unsqueeze(1) * ph).sum(dim=0)
+        return torch.view_as_real(out).contiguous()
+
     def field_sumsq(self, entries) -> torch.Tensor:
         """(R,) float64: per entry the sum over its box of the squares of the
         field, converted to fp64 first, added to the entry's row (ops/energy.py

@@ -163,8 +163,8 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
     if status != EXIT_OK:
         return status
     log.set_level(settings.logLevel)
-    if (settings.doUseDft or settings.doUseNtffDft or settings.doUseFlux or settings.doUseEnergy
-            or settings.stopDecayBy != 0):
+    if (settings.doUseDft or settings.doUseNtffDft or settings.doUseFlux or settings.doUseFarfield
+            or settings.doUseEnergy or settings.stopDecayBy != 0):
         # refused before anything is set up, never a silent fallback (models/dft.py, models/energy.py)
         from .models.dft import refuse_config
         from .models.energy import refuse_energy_config
@@ -237,12 +237,24 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         flux_reported = [None, None]  # (step, result) of the last periodic report
         if scheme.cfg.flux_report_step > 0:
             scheme.add_periodic(scheme.cfg.flux_report_step, 0, flux_hook)
+    farfield = None
+    if scheme.cfg.use_farfield:
+        from .models.farfield import farfield_from_config
+        from .utils.assertions import FdtdError
+        try:
+            # on the flux monitor's box it reads that monitor's slabs: sampled once (models/farfield.py)
+            farfield = farfield_from_config(scheme, flux)
+        except FdtdError as e:
+            out.write("ERROR: %s\n" % e)
+            if dist is not None:
+                dist.destroy_process_group()
+            return EXIT_ERROR
     energy = None
     if scheme.cfg.use_energy:
         from .models.energy import energy_from_config
         from .utils.assertions import FdtdError
         try:
-            # after the DFT / flux monitors: the automatic step follows theirs (models/energy.py)
+            # after the DFT / flux / far-field monitors: the automatic step follows theirs (models/energy.py)
             energy = energy_from_config(scheme)
         except FdtdError as e:
             out.write("ERROR: %s\n" % e)
@@ -298,6 +310,13 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         flux_result = flux_reported[1]  # the last step's periodic report is the final one
     elif flux is not None:
         flux_result = flux.report(scheme.t, out if rank == 0 else open(os.devnull, "w"))
+    farfield_result = None
+    if farfield is not None:
+        # every rank: a decomposed run gathers the slabs on rank 0, which evaluates and reports
+        farfield_result = farfield.report(scheme.t, out if rank == 0 else open(os.devnull, "w"))
+        if farfield_result is not None and settings.doSaveRes:
+            from .io.dump import dump_farfield
+            dump_farfield(farfield_result, farfield.wavelengths, scheme.t, settings.outputDir)
     energy_result = None
     if energy is not None:
         # every rank: the series is summed over the ranks
@@ -338,6 +357,8 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                     rec["dft"]["ntff"] = monitors["ntff"].info()
             if flux_result is not None:
                 rec["flux"] = flux.info(flux_result)
+            if farfield_result is not None:
+                rec["farfield"] = farfield.info(farfield_result)
             if energy_result is not None:
                 rec["energy"] = energy.info(energy_result)
             if breakdown is not None:

@@ -190,6 +190,8 @@ class Settings:
             self.dftSizeY = self.dftSizeZ = self.dftSizeX
         elif a == "--same-size-flux":
             self.fluxSizeY = self.fluxSizeZ = self.fluxSizeX
+        elif a == "--same-size-farfield":
+            self.farfieldSizeY = self.farfieldSizeZ = self.farfieldSizeX
         elif a == "--same-size-energy":
             self.energySizeY = self.energySizeZ = self.energySizeX
         elif a == "--same-size-topology":
