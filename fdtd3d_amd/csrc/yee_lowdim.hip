@@ -11,6 +11,15 @@
 
 #include "common.h"
 
+// Test hook: the workgroups a window should hold before its automatic x chunk
+// stops halving (xchunk2d).  Nothing in the package sets it.  At the default a
+// grid needs about a million cells before two windows of a launch get
+// different chunks; tests/test_plain_gpu.py lowers it so that a small grid
+// reaches that form of the Win2 table.  Process-wide, restored by the test.
+static int g_lowdim_wgs = 2048;
+
+FDTD_API void fdtd_set_lowdim_wgs(int wgs) { g_lowdim_wgs = wgs > 0 ? wgs : 2048; }
+
 namespace {
 
 constexpr int TX = 64;
@@ -168,11 +177,11 @@ __global__ void k_1d_h(T* __restrict__ hy, const T* __restrict__ ez, const T* __
 }
 
 // rows per thread along x: 16, fewer on thin windows (hybrid shell, PML
-// slabs) until the launch holds >= 2048 workgroups
+// slabs) until the launch holds >= g_lowdim_wgs (2048) workgroups
 inline int xchunk2d(const Box3& b, int req) {
   if (req > 0) return req;
   int xc = 16;
-  while (xc > 1 && (long long)cdiv(b.hi[1] - b.lo[1], TX) * cdiv(cdiv(b.hi[0] - b.lo[0], xc), TY) < 2048) xc /= 2;
+  while (xc > 1 && (long long)cdiv(b.hi[1] - b.lo[1], TX) * cdiv(cdiv(b.hi[0] - b.lo[0], xc), TY) < g_lowdim_wgs) xc /= 2;
   return xc;
 }
 
