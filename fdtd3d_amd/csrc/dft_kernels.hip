@@ -20,6 +20,7 @@
 // are computed by the host in fp64 once per sample and passed BY VALUE in the
 // kernel arguments, so they sit in SGPRs.
 #include "common.h"
+#include "monitor_dev.h"
 
 namespace {
 
@@ -106,15 +107,10 @@ __device__ __forceinline__ void dft_entry(const DftEnt& e, int blk, const DftTw<
 
 template <typename T, int K>
 __global__ __launch_bounds__(256) void k_dft_accum(const DftEnt* __restrict__ tab, int n, DftTw<T, K> tw) {
-  // the block's entry: binary search over blk0 (wave-uniform scalar loads)
-  typedef const __attribute__((address_space(4))) DftEnt* EntPtr;
-  const EntPtr E = (EntPtr)tab;
+  // the block's entry: binary search over blk0 (monitor_dev.h)
+  const mon::ConstTab<DftEnt> E = (mon::ConstTab<DftEnt>)tab;
   const int b = (int)blockIdx.x;
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (E[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-  }
+  const int lo = mon::entry_of_block(tab, n, b);
   DftEnt e;  // (field by field: the constant-address-space entry has no implicit copy)
   e.f = E[lo].f;
   e.acc = E[lo].acc;

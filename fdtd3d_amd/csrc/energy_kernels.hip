@@ -21,8 +21,9 @@
 // row in a fixed order.  No atomics: the same input gives the same bits.
 //
 // The kernel checks nothing beyond the box: the host verifies every entry
-// against its tensor (ops/hip_ops.py field_sumsq).
+// against its tensor (ops/hip_monitors.py field_sumsq).
 #include "common.h"
+#include "monitor_dev.h"
 
 namespace {
 
@@ -46,8 +47,7 @@ static_assert(sizeof(EnergyEnt) == 64, "EnergyEnt layout (ops/energy.py ENERGY_E
 // the block's sum of v in thread 0 (fixed order)
 __device__ __forceinline__ double energy_block_sum(double v, double* red) {
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  v = mon::wave_sum(v);
   if (lane == 0) red[wave] = v;
   __syncthreads();
   double s = red[0];
@@ -112,15 +112,10 @@ template <typename T>
 __global__ __launch_bounds__(EN_BLOCK) void k_energy_partial(const EnergyEnt* __restrict__ tab, int n, int rows_blk,
                                                               double* __restrict__ partials) {
   __shared__ double red[EN_WAVES];
-  // the block's entry: binary search over blk0 (wave-uniform scalar loads)
-  typedef const __attribute__((address_space(4))) EnergyEnt* EntPtr;
-  const EntPtr E = (EntPtr)tab;
+  // the block's entry: binary search over blk0 (monitor_dev.h)
+  const mon::ConstTab<EnergyEnt> E = (mon::ConstTab<EnergyEnt>)tab;
   const int b = (int)blockIdx.x;
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (E[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-  }
+  const int lo = mon::entry_of_block(tab, n, b);
   EnergyEnt e;  // (field by field: the constant-address-space entry has no implicit copy)
   e.f = E[lo].f;
   e.sx = E[lo].sx;

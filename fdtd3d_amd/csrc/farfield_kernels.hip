@@ -16,8 +16,8 @@
 // all of them.  A thread owns one direction for one (group, wavelength, cell
 // split); a block covers FAR_BLOCK directions.  The block walks its cells in
 // chunks of FAR_BLOCK, linearised (x, y, z) with z fastest: its threads load
-// and average one cell each (the flux_kernels.hip operand logic, with the
-// aligned 16-byte group load on z-normal faces) and park (re, im) of every
+// and average one cell each (monitor_dev.h face_avg, with the aligned 16-byte
+// group load on z-normal faces) and park (re, im) of every
 // current in LDS as fp64; then every thread loops over the chunk, reading LDS
 // at a wave-uniform address (a broadcast: no bank conflicts).  The phase is an
 // exact fp64 sincos at the start of every face row and of every chunk, and in
@@ -32,8 +32,9 @@
 //
 // The kernel checks nothing beyond the face extent and the direction count:
 // the host verifies every operand's reach against its accumulator block
-// (ops/hip_ops.py dft_farfield).
+// (ops/hip_monitors.py dft_farfield).
 #include "common.h"
+#include "monitor_dev.h"
 
 namespace {
 
@@ -58,60 +59,16 @@ struct FarEnt {
 };
 static_assert(sizeof(FarEnt) == 216, "FarEnt layout (ops/dft.py FAR_ENT_SIZE)");
 
-// s += the one or two z samples of a row at z (in this order)
-template <typename T>
-__device__ __forceinline__ void far_row(const T* __restrict__ row, int z, bool two, bool zvec, double& s) {
-  constexpr int V = 16 / sizeof(T);
-  typedef T VT __attribute__((ext_vector_type(V)));
-  if (zvec) {
-    const int g = z & ~(V - 1), l = z - g;
-    const VT v = *reinterpret_cast<const VT*>(row + g);
-    T a = v[0], b = v[V - 1];
-#pragma unroll
-    for (int m = 1; m < V; ++m) a = (m == l) ? v[m] : a;
-    s = __dadd_rn(s, (double)a);
-    if (two) {
-      if (l + 1 < V) {
-#pragma unroll
-        for (int m = 1; m < V; ++m) b = (m == l + 1) ? v[m] : b;
-      } else {
-        b = row[z + 1];  // the next group (the padded extent holds it)
-      }
-      s = __dadd_rn(s, (double)b);
-    }
-  } else {
-    s = __dadd_rn(s, (double)row[z]);
-    if (two) s = __dadd_rn(s, (double)row[z + 1]);
-  }
-}
-
-// face-centre average of one accumulator plane at the thread's cell
-template <typename T>
-__device__ __forceinline__ double far_operand(const T* __restrict__ p, int sx, int sy, int z, int flags) {
-  const int nx = (flags & 1) + 1, ny = ((flags >> 1) & 1) + 1;
-  const bool two = (flags >> 2) & 1, zvec = (flags >> 3) & 1;
-  double s = 0.0;
-  for (int ox = 0; ox < nx; ++ox)
-    for (int oy = 0; oy < ny; ++oy) far_row<T>(p + (size_t)ox * sx + (size_t)oy * sy, z, two, zvec, s);
-  const int cnt = nx * ny * (two ? 2 : 1);
-  return s * (1.0 / cnt);  // a power of two: exact
-}
-
 template <typename T>
 __global__ __launch_bounds__(FAR_BLOCK) void k_far_partial(const FarEnt* __restrict__ tab, int n, int K, int A,
                                                             int tiles, const double* __restrict__ dirs,
                                                             const double* __restrict__ wn, double dx,
                                                             double* __restrict__ partials) {
   __shared__ double val[FAR_BLOCK][2 * FAR_GROUP];  // (re, im) of every current of the chunk's cells
-  // the block's entry: binary search over blk0 (wave-uniform scalar loads)
-  typedef const __attribute__((address_space(4))) FarEnt* EntPtr;
-  const EntPtr E = (EntPtr)tab;
+  // the block's entry: binary search over blk0 (monitor_dev.h)
+  const mon::ConstTab<FarEnt> E = (mon::ConstTab<FarEnt>)tab;
   const int b = (int)blockIdx.x;
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (E[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-  }
+  const int lo = mon::entry_of_block(tab, n, b);
   const int e0 = E[lo].ext[0], e1 = E[lo].ext[1], e2 = E[lo].ext[2];
   const int ncur = E[lo].ncur, splits = E[lo].splits;
   const int local = b - E[lo].blk0;
@@ -150,8 +107,8 @@ __global__ __launch_bounds__(FAR_BLOCK) void k_far_partial(const FarEnt* __restr
           const T* p = (const T*)E[lo].acc[c] + (size_t)(2 * q) * plane + (size_t)(E[lo].first[c][0] + i) * sx +
                        (size_t)(E[lo].first[c][1] + j) * sy;
           const int z = E[lo].first[c][2] + k;
-          val[tid][2 * c] = far_operand<T>(p, sx, sy, z, fl);
-          val[tid][2 * c + 1] = far_operand<T>(p + plane, sx, sy, z, fl);
+          val[tid][2 * c] = mon::face_avg<T>(p, sx, sy, z, fl, (fl >> 3) & 1);
+          val[tid][2 * c + 1] = mon::face_avg<T>(p + plane, sx, sy, z, fl, (fl >> 3) & 1);
         }
       }
     }

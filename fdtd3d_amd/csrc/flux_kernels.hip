@@ -22,8 +22,9 @@
 // gives the same bits.
 //
 // The kernel checks nothing beyond the face extent: the host verifies every
-// entry's reach against its accumulator block (ops/hip_ops.py dft_flux).
+// entry's reach against its accumulator block (ops/hip_monitors.py dft_flux).
 #include "common.h"
+#include "monitor_dev.h"
 
 namespace {
 
@@ -46,45 +47,6 @@ struct FluxEnt {
 };
 static_assert(sizeof(FluxEnt) == 112, "FluxEnt layout (ops/dft.py FLUX_ENT_SIZE)");
 
-// s += the one or two z samples of a row at z (in this order)
-template <typename T, bool ZVEC>
-__device__ __forceinline__ void flux_row(const T* __restrict__ row, int z, bool two, double& s) {
-  constexpr int V = 16 / sizeof(T);
-  typedef T VT __attribute__((ext_vector_type(V)));
-  if (ZVEC) {
-    const int g = z & ~(V - 1), l = z - g;
-    const VT v = *reinterpret_cast<const VT*>(row + g);
-    T a = v[0], b = v[V - 1];
-#pragma unroll
-    for (int m = 1; m < V; ++m) a = (m == l) ? v[m] : a;
-    s = __dadd_rn(s, (double)a);
-    if (two) {
-      if (l + 1 < V) {
-#pragma unroll
-        for (int m = 1; m < V; ++m) b = (m == l + 1) ? v[m] : b;
-      } else {
-        b = row[z + 1];  // the next group (the padded extent holds it)
-      }
-      s = __dadd_rn(s, (double)b);
-    }
-  } else {
-    s = __dadd_rn(s, (double)row[z]);
-    if (two) s = __dadd_rn(s, (double)row[z + 1]);
-  }
-}
-
-// face-centre average of one operand plane at the thread's cell
-template <typename T, bool ZVEC>
-__device__ __forceinline__ double flux_operand(const T* __restrict__ p, int sx, int sy, int z, int avg) {
-  const int nx = (avg & 1) + 1, ny = ((avg >> 1) & 1) + 1;
-  const bool two = (avg >> 2) & 1;
-  double s = 0.0;
-  for (int ox = 0; ox < nx; ++ox)
-    for (int oy = 0; oy < ny; ++oy) flux_row<T, ZVEC>(p + (size_t)ox * sx + (size_t)oy * sy, z, two, s);
-  const int cnt = nx * ny * (two ? 2 : 1);
-  return s * (1.0 / cnt);  // a power of two: exact
-}
-
 template <typename T, bool ZVEC>
 __device__ __forceinline__ void flux_cell(const FluxEnt& e, int idx, int K, double (&acc)[FLUX_MAX_K]) {
   const int k = idx % e.ext[2], jj = idx / e.ext[2];
@@ -96,10 +58,10 @@ __device__ __forceinline__ void flux_cell(const FluxEnt& e, int idx, int K, doub
 #pragma unroll
   for (int q = 0; q < FLUX_MAX_K; ++q) {
     if (q < K) {
-      const double er = flux_operand<T, ZVEC>(E + (size_t)(2 * q) * e.eplane, e.esx, e.esy, ze, e.eavg);
-      const double ei = flux_operand<T, ZVEC>(E + (size_t)(2 * q + 1) * e.eplane, e.esx, e.esy, ze, e.eavg);
-      const double hr = flux_operand<T, ZVEC>(H + (size_t)(2 * q) * e.hplane, e.hsx, e.hsy, zh, e.havg);
-      const double hi = flux_operand<T, ZVEC>(H + (size_t)(2 * q + 1) * e.hplane, e.hsx, e.hsy, zh, e.havg);
+      const double er = mon::face_avg<T>(E + (size_t)(2 * q) * e.eplane, e.esx, e.esy, ze, e.eavg, ZVEC);
+      const double ei = mon::face_avg<T>(E + (size_t)(2 * q + 1) * e.eplane, e.esx, e.esy, ze, e.eavg, ZVEC);
+      const double hr = mon::face_avg<T>(H + (size_t)(2 * q) * e.hplane, e.hsx, e.hsy, zh, e.havg, ZVEC);
+      const double hi = mon::face_avg<T>(H + (size_t)(2 * q + 1) * e.hplane, e.hsx, e.hsy, zh, e.havg, ZVEC);
       acc[q] = sg * __dadd_rn(__dmul_rn(er, hr), __dmul_rn(ei, hi));
     }
   }
@@ -111,9 +73,7 @@ __device__ __forceinline__ void flux_block_sums(const double (&acc)[FLUX_MAX_K],
 #pragma unroll
   for (int q = 0; q < FLUX_MAX_K; ++q) {
     if (q < K) {
-      double v = acc[q];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+      const double v = mon::wave_sum(acc[q]);
       if (lane == 0) red[wave][q] = v;
     }
   }
@@ -124,15 +84,10 @@ template <typename T>
 __global__ __launch_bounds__(FLUX_BLOCK) void k_flux_partial(const FluxEnt* __restrict__ tab, int n, int K,
                                                               double* __restrict__ partials) {
   __shared__ double red[FLUX_WAVES][FLUX_MAX_K];
-  // the block's entry: binary search over blk0 (wave-uniform scalar loads)
-  typedef const __attribute__((address_space(4))) FluxEnt* EntPtr;
-  const EntPtr E = (EntPtr)tab;
+  // the block's entry: binary search over blk0 (monitor_dev.h)
+  const mon::ConstTab<FluxEnt> E = (mon::ConstTab<FluxEnt>)tab;
   const int b = (int)blockIdx.x;
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (E[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-  }
+  const int lo = mon::entry_of_block(tab, n, b);
   FluxEnt e;  // (field by field: the constant-address-space entry has no implicit copy)
   e.e = E[lo].e;
   e.h = E[lo].h;

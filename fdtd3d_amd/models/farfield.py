@@ -1,10 +1,9 @@
 """Far-field monitor: radiation patterns, radiated power, directivity and RCS
 per wavelength from the phasors of a running-DFT monitor.
 
-A :class:`FarFieldMonitor` watches the box ``margin`` cells inside the grid
-borders of a 3D run -- the slabs and face-centre sampling plans of the NTFF
-surface (models/ntff.py ``_faces``, ``_sample_plan``, ``_plan_box``) -- through
-a :class:`~.dft.DftMonitor` with ``h_time="half"``, its own or the one of a
+A :class:`FarFieldMonitor` is a :class:`~.surface.SurfaceMonitor`: it watches
+the box ``margin`` cells inside the grid borders of a 3D run through a
+:class:`~.dft.DftMonitor` with ``h_time="half"``, its own or the one of a
 :class:`~.flux.FluxMonitor` on the same box.  The tangential phasors on a face
 with outward normal ``n`` are the equivalent currents ``J = n x H``, ``M = -n x
 E``; their radiation vectors in the direction ``rhat``, with the project's
@@ -24,7 +23,7 @@ the diagram of ``--use-ntff``).  From it: :meth:`FarFieldMonitor.total_power`
 (Gauss-Legendre in ``cos theta`` x uniform ``phi``), :meth:`directivity` ``= 4
 pi U / total_power`` and, in TF/SF runs with the box outside the TF/SF box,
 the bistatic :meth:`rcs` ``= 4 pi U / incident`` in m^2, ``incident`` the
-intensity of the source signal at every wavelength as in models/flux.py -- a
+intensity of the source signal at every wavelength (models/surface.py) -- a
 sine source over whole periods and a Gaussian pulse take the same path.
 
 The sampling window must cover whole periods of a steady state or the whole
@@ -33,7 +32,6 @@ pulse (models/flux.py).
 
 from __future__ import annotations
 
-import math
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -43,8 +41,8 @@ from ..ops.dft import FarTerm, FarTerms
 from ..utils.assertions import FdtdError
 from ..utils.constants import PI
 from .dft import DftMonitor, parse_wavelengths
-from .flux import TFSF_MIN_DISTANCE, slab_operand
-from .ntff import ETA0, _faces, _sample_plan, ntff_requests
+from .ntff import ETA0, _sample_plan
+from .surface import SurfaceMonitor
 
 
 def farfield_from_config(scheme, flux=None) -> Optional["FarFieldMonitor"]:
@@ -83,85 +81,30 @@ def report_grid(ntheta: int, nphi: int):
             torch.arange(nphi, dtype=torch.float64) * (2 * PI / nphi))
 
 
-class FarFieldMonitor:
+class FarFieldMonitor(SurfaceMonitor):
     """Far field of the box ``margin`` cells inside the grid borders at
     ``wavelengths``; ``step`` (0 = automatic) and ``start`` as for
     :class:`~.dft.DftMonitor`.  ``dft``: an existing monitor over the same
     slabs (``ntff_requests(size, margin)``, ``h_time="half"``, the same
     wavelengths) that something else samples, e.g. ``FluxMonitor.dft``."""
 
+    box_name = "far-field box"
+
     def __init__(self, scheme, margin: Sequence[int], wavelengths: Sequence[float], step: int = 0, start: int = 0,
                  dft: Optional[DftMonitor] = None, register: bool = True):
-        cfg = scheme.cfg
-        if cfg.scheme != "3d":
-            raise FdtdError("FarFieldMonitor: 3D runs only (got the %s scheme)" % cfg.scheme)
-        if scheme.planes != 1 or cfg.complex_values:
-            raise FdtdError("FarFieldMonitor: real-valued runs only (a complex run already carries the phasor)")
-        if cfg.use_amp_mode:
-            raise FdtdError("FarFieldMonitor: not with amplitude mode")
-        size = tuple(cfg.size)
-        self.margin = tuple(int(m) for m in margin)
-        if any(m < 0 for m in self.margin) or any(size[a] - 2 * self.margin[a] <= 0 for a in range(3)):
-            raise FdtdError("FarFieldMonitor: the box %s cells inside the grid %s is empty" % (self.margin, size))
-        self.label = self._label(cfg)
-        self.size = size
-        self.faces = _faces(size, self.margin)
-        self.scheme = scheme
-        self.dx = float(scheme.dx)
-        requests = ntff_requests(size, self.margin)
-        self.shared = dft is not None
-        if dft is None:
-            dft = DftMonitor(scheme, requests, wavelengths, step, start, "half", register=False)
-        elif (dft.requests != requests or dft.h_time != "half"
-              or dft.wavelengths != [float(w) for w in wavelengths]):
-            raise FdtdError("FarFieldMonitor: the shared DFT monitor does not sample this box's slabs at these "
-                            "wavelengths with h_time='half'")
-        self.dft = dft
-        self.wavelengths, self.omegas = dft.wavelengths, dft.omegas
+        super().__init__(scheme, margin, wavelengths, step, start, dft, register)
         self.wavenumbers = [2 * PI / w for w in self.wavelengths]
-        self.step, self.start = dft.step, dft.start
-        self._n_src = 0
-        self._src = [[0.0, 0.0] for _ in self.wavelengths]  # running DFT of the source signal
-        self._terms: Optional[FarTerms] = None
-        if register:
-            scheme.add_periodic(self.step, self.start % self.step, self.sample)
-
-    @property
-    def samples(self) -> int:
-        return self.dft.samples
 
     def _label(self, cfg) -> str:
         """``radiated`` without TF/SF, else ``scattered``: the box must lie
-        outside the TF/SF box, at least ``TFSF_MIN_DISTANCE`` cells from its
-        faces (the far field of the total field is no scattering pattern)."""
-        if not cfg.use_tfsf:
-            return "radiated"
-        d = [self.margin[a] - int(cfg.tfsf_size[a]) for a in range(3)]
-        if any(abs(v) < TFSF_MIN_DISTANCE for v in d):
-            raise FdtdError("FarFieldMonitor: the far-field box (margin %s) lies less than %d cells from the TF/SF "
-                            "faces (margin %s): the face-centre averages would straddle the total / scattered boundary"
-                            % (self.margin, TFSF_MIN_DISTANCE, tuple(cfg.tfsf_size)))
-        if all(v < 0 for v in d):
-            return "scattered"
-        if all(v > 0 for v in d):
+        outside the TF/SF box (the far field of the total field is no
+        scattering pattern)."""
+        place = self._placement(cfg)
+        if place == "inside":
             raise FdtdError("FarFieldMonitor: the far-field box (margin %s) lies inside the TF/SF box (margin %s): "
                             "the far field of the total field is not a scattering pattern"
                             % (self.margin, tuple(cfg.tfsf_size)))
-        raise FdtdError("FarFieldMonitor: the far-field box (margin %s) crosses the TF/SF box (margin %s)"
-                        % (self.margin, tuple(cfg.tfsf_size)))
-
-    # ------------------------------------------------------------------ sampling
-    def sample(self, scheme, t: int) -> None:
-        if t < self.start or (t - self.start) % self.step:
-            return
-        if not self.shared:
-            self.dft.sample(scheme, t)
-        te = self.dft.sample_times(scheme, t)[0]
-        v = scheme.source_value(t - 1, 0)
-        for acc, w in zip(self._src, self.omegas):
-            acc[0] += v * math.cos(w * te)
-            acc[1] += v * math.sin(w * te)
-        self._n_src += 1
+        return "radiated" if place == "none" else "scattered"
 
     # ------------------------------------------------------------------- results
     def _build_terms(self, gathered: bool) -> Optional[FarTerms]:
@@ -178,27 +121,19 @@ class FarFieldMonitor:
             for slot, sign, comp in ((a2, sc, "H" + "xyz"[a1]), (a1, -sc, "H" + "xyz"[a2]),
                                      (3 + a2, -sc, "E" + "xyz"[a1]), (3 + a1, sc, "E" + "xyz"[a2])):
                 plan = _sample_plan(comp, axis, x0, lo, hi)
-                op = slab_operand(self.dft, self.scheme, comp, plan, gathered)
+                op = self._operand(comp, plan, gathered)
                 if op is None:
                     missing = True
                     continue
                 terms.add(FarTerm(slot, sign, [n for _, n, _ in plan], op, pos0))
         return None if missing else terms
 
-    def _gathered(self) -> bool:
-        return self.scheme.halo is not None and self.scheme.halo.comm.world > 1
-
     def vectors_many(self, dir_sets: Sequence[torch.Tensor]) -> Optional[List[torch.Tensor]]:
         """:meth:`vectors` of several direction sets from one evaluation (a
         decomposed run gathers the accumulators once)."""
-        if self._gathered():
-            terms = self._build_terms(True)  # the sums have moved on: gathered anew at every call
-            if terms is None:
-                return None
-        else:
-            if self._terms is None:
-                self._terms = self._build_terms(False)
-            terms = self._terms
+        terms = self._current_terms()
+        if terms is None:
+            return None
         sets = [torch.as_tensor(d, dtype=torch.float64).reshape(-1, 3) for d in dir_sets]
         raw = self.scheme.ops.dft_farfield(terms, torch.cat(sets), torch.tensor(self.wavenumbers, dtype=torch.float64))
         vec = torch.view_as_complex(raw.cpu().contiguous()) * (self.dx * self.dx * 2.0 / max(1, self.samples))
@@ -263,14 +198,6 @@ class FarFieldMonitor:
         """(K, T, P) ``4 pi U / total_power``."""
         r = self.evaluate(thetas, phis)
         return None if r is None else r["directivity"]
-
-    def incident(self) -> torch.Tensor:
-        """(K,) ``|A_src|^2 / (2 eta0)`` in W / m^2, ``A_src`` the phasor of
-        the source signal over the monitor's samples (models/flux.py
-        ``FluxMonitor.incident``)."""
-        n = max(1, self._n_src)
-        return torch.tensor([((2.0 / n) ** 2) * (re * re + im * im) / (2.0 * ETA0) for re, im in self._src],
-                            dtype=torch.float64)
 
     def rcs(self, thetas, phis) -> Optional[torch.Tensor]:
         """(K, T, P) bistatic radar cross-section ``4 pi U / incident`` in

@@ -1,12 +1,11 @@
 """Poynting-flux monitor: time-averaged power through a closed box, per
 wavelength, from the phasors of a running-DFT monitor.
 
-A :class:`FluxMonitor` watches the box ``margin`` cells inside the grid
-borders of a 3D run.  It owns a :class:`~.dft.DftMonitor` over the tangential
-E and H slabs around the six faces -- the slabs and face-centre sampling plans
-of the NTFF surface (models/ntff.py ``_faces``, ``_sample_plan``,
-``_plan_box``) -- with ``h_time="half"``, so E and H phasors share one time
-origin, which their product needs.  Through a face with normal axis ``a``,
+A :class:`FluxMonitor` is a :class:`~.surface.SurfaceMonitor`: it watches the
+box ``margin`` cells inside the grid borders of a 3D run and owns a
+:class:`~.dft.DftMonitor` over the tangential E and H slabs around the six
+faces with ``h_time="half"``, so E and H phasors share one time origin, which
+their product needs.  Through a face with normal axis ``a``,
 ``(b, c)`` the cyclic successors of ``a``,
 
     P = sign dx^2 1/2 (2/N)^2 sum over the face cells of
@@ -35,17 +34,15 @@ power, carry the truncation.
 
 from __future__ import annotations
 
-import math
 from typing import Dict, Optional, Sequence
 
 import torch
 
-from ..ops.dft import FluxOperand, FluxTerm, FluxTerms, acc_shape, vec_width, z_pad
+from ..ops.dft import FluxTerm, FluxTerms
 from ..utils.assertions import FdtdError
-from .dft import DftMonitor, parse_wavelengths
-from .ntff import ETA0, _faces, _plan_box, _sample_plan, ntff_requests
-
-TFSF_MIN_DISTANCE = 2  # cells between a flux face and the TF/SF face: the averages must not straddle it
+from .dft import parse_wavelengths
+from .ntff import _sample_plan
+from .surface import TFSF_MIN_DISTANCE, SurfaceMonitor, slab_operand  # noqa: F401 (both importable from here)
 
 
 def flux_from_config(scheme) -> Optional["FluxMonitor"]:
@@ -62,99 +59,25 @@ def flux_from_config(scheme) -> Optional["FluxMonitor"]:
                        cfg.dft_step, cfg.dft_start)
 
 
-def slab_operand(dft: DftMonitor, scheme, comp: str, plan, gathered: bool) -> Optional[FluxOperand]:
-    """The accumulators of (comp, the plan's box) of ``dft`` in the padded
-    layout of a serial monitor, with the plan's first sample and averaging
-    axes; ``gathered``: collected from the ranks on rank 0 (None elsewhere).
-    Shared with models/farfield.py."""
-    box = _plan_box(plan)
-    i = dft.index((comp, box))
-    avg = [len(offs) == 2 for _, _, offs in plan]
-    if not gathered:
-        e = dft.entries.rows[i]
-        return FluxOperand(e.acc, (0, 0, e.box[0][2] - z_pad(e.box, vec_width(e.acc.dtype))[0]), avg)
-    raw = dft.gather_accumulators(scheme, i)
-    if raw is None:
-        return None
-    v = vec_width(raw.dtype)
-    z0 = z_pad(box, v)[0]
-    acc = torch.zeros(acc_shape(box, raw.shape[0], v), dtype=raw.dtype, device=raw.device)
-    acc[..., box[0][2] - z0:box[1][2] - z0] = raw
-    return FluxOperand(acc, (0, 0, box[0][2] - z0), avg)
-
-
-class FluxMonitor:
+class FluxMonitor(SurfaceMonitor):
     """Power through the box ``margin`` cells inside the grid borders at
     ``wavelengths``; ``step`` (0 = automatic, passes between samples stay
     blocked) and ``start`` as for :class:`~.dft.DftMonitor`.  The window must
     cover whole periods of a steady state, or the whole pulse (module
     docstring)."""
 
+    box_name = "flux box"
+
     def __init__(self, scheme, margin: Sequence[int], wavelengths: Sequence[float], step: int = 0, start: int = 0,
                  register: bool = True):
-        cfg = scheme.cfg
-        if cfg.scheme != "3d":
-            raise FdtdError("FluxMonitor: 3D runs only (got the %s scheme)" % cfg.scheme)
-        if scheme.planes != 1 or cfg.complex_values:
-            raise FdtdError("FluxMonitor: real-valued runs only (a complex run already carries the phasor)")
-        if cfg.use_amp_mode:
-            raise FdtdError("FluxMonitor: not with amplitude mode")
-        size = tuple(cfg.size)
-        self.margin = tuple(int(m) for m in margin)
-        if any(m < 0 for m in self.margin) or any(size[a] - 2 * self.margin[a] <= 0 for a in range(3)):
-            raise FdtdError("FluxMonitor: the box %s cells inside the grid %s is empty" % (self.margin, size))
-        self.label = self._label(cfg)
-        self.faces = _faces(size, self.margin)
-        self.scheme = scheme
-        self.dx = float(scheme.dx)
-        self.dft = DftMonitor(scheme, ntff_requests(size, self.margin), wavelengths, step, start, "half",
-                              register=False)
-        self.wavelengths, self.omegas = self.dft.wavelengths, self.dft.omegas
-        self.step, self.start = self.dft.step, self.dft.start
-        self._src = [[0.0, 0.0] for _ in self.wavelengths]  # running DFT of the source signal
-        self._terms: Optional[FluxTerms] = None
-        if register:
-            scheme.add_periodic(self.step, self.start % self.step, self.sample)
-
-    @property
-    def samples(self) -> int:
-        return self.dft.samples
+        super().__init__(scheme, margin, wavelengths, step, start, None, register)
 
     def _label(self, cfg) -> str:
         """``radiated`` without TF/SF, else ``scattered`` (box outside the
-        TF/SF box) or ``absorbed`` (inside); refuses a box closer than
-        ``TFSF_MIN_DISTANCE`` cells to the TF/SF faces or crossing them."""
-        if not cfg.use_tfsf:
-            return "radiated"
-        d = [self.margin[a] - int(cfg.tfsf_size[a]) for a in range(3)]
-        if any(abs(v) < TFSF_MIN_DISTANCE for v in d):
-            raise FdtdError("FluxMonitor: the flux box (margin %s) lies less than %d cells from the TF/SF faces "
-                            "(margin %s): the face-centre averages would straddle the total / scattered boundary"
-                            % (self.margin, TFSF_MIN_DISTANCE, tuple(cfg.tfsf_size)))
-        if all(v > 0 for v in d):
-            return "absorbed"
-        if all(v < 0 for v in d):
-            return "scattered"
-        raise FdtdError("FluxMonitor: the flux box (margin %s) crosses the TF/SF box (margin %s)"
-                        % (self.margin, tuple(cfg.tfsf_size)))
-
-    # ------------------------------------------------------------------ sampling
-    def sample(self, scheme, t: int) -> None:
-        if t < self.start or (t - self.start) % self.step:
-            return
-        self.dft.sample(scheme, t)
-        te = self.dft.sample_times(scheme, t)[0]
-        v = scheme.source_value(t - 1, 0)
-        for acc, w in zip(self._src, self.omegas):
-            acc[0] += v * math.cos(w * te)
-            acc[1] += v * math.sin(w * te)
+        TF/SF box) or ``absorbed`` (inside)."""
+        return {"none": "radiated", "inside": "absorbed", "outside": "scattered"}[self._placement(cfg)]
 
     # ------------------------------------------------------------------- results
-    def _operand(self, comp: str, plan, gathered: bool) -> Optional[FluxOperand]:
-        """The accumulators of (comp, the plan's box) in the padded layout of a
-        serial monitor, with the plan's first sample and averaging axes."""
-        return slab_operand(self.dft, self.scheme, comp, plan, gathered)
-
     def _build_terms(self, gathered: bool) -> Optional[FluxTerms]:
         terms = FluxTerms(len(self.wavelengths), len(self.faces))
         missing = False
@@ -176,17 +99,10 @@ class FluxMonitor:
         the order of ``_faces`` (-x, +x, -y, +y, -z, +z), outward positive.
         Decomposed runs gather the slabs' raw accumulators on rank 0, which
         runs the same evaluation; the other ranks return None."""
-        scheme = self.scheme
-        gathered = scheme.halo is not None and scheme.halo.comm.world > 1
-        if gathered:
-            terms = self._build_terms(True)  # the sums have moved on: gathered anew at every call
-            if terms is None:
-                return None
-        else:
-            if self._terms is None:
-                self._terms = self._build_terms(False)
-            terms = self._terms
-        raw = scheme.ops.dft_flux(terms)
+        terms = self._current_terms()
+        if terms is None:
+            return None
+        raw = self.scheme.ops.dft_flux(terms)
         n = max(1, self.samples)
         return raw.cpu() * (self.dx * self.dx * 0.5 * (2.0 / n) ** 2)
 
@@ -194,15 +110,6 @@ class FluxMonitor:
         """(K,) net outward power in watts (None off rank 0)."""
         p = self.power()
         return None if p is None else p.sum(dim=0)
-
-    def incident(self) -> torch.Tensor:
-        """(K,) ``|A_src|^2 / (2 eta0)`` in W / m^2, ``A_src`` the phasor of
-        the source signal over the monitor's samples: ``1 / (2 eta0)`` for
-        the sine source over whole periods, the pulse spectrum for a Gaussian
-        source."""
-        n = max(1, self.samples)
-        return torch.tensor([((2.0 / n) ** 2) * (re * re + im * im) / (2.0 * ETA0) for re, im in self._src],
-                            dtype=torch.float64)
 
     def cross_section(self) -> Optional[torch.Tensor]:
         """(K,) m^2: scattered (box outside the TF/SF box) or absorbed (box

@@ -13,7 +13,7 @@ accumulators: products of face-centre averages summed over the faces of a box
 (models/flux.py; csrc/flux_kernels.hip).  ``FarTerms`` describe what
 ``dft_farfield(terms, dirs, wavenumbers)`` evaluates from them: the radiation
 vectors of the equivalent currents on the faces (models/farfield.py; csrc/
-farfield_kernels.hip).
+farfield_kernels.hip).  HIP ops and device tables: ops/hip_monitors.py.
 """
 
 from __future__ import annotations
@@ -73,7 +73,17 @@ class DftEntry:
         return self.acc[..., self.box[0][2] - z0:self.box[1][2] - z0]
 
 
-class DftEntries:
+class _Rows:
+    """A monitor's entries or terms: iterates over, and counts, its ``rows``."""
+
+    def __iter__(self):
+        return iter(self.rows)
+
+    def __len__(self):
+        return len(self.rows)
+
+
+class DftEntries(_Rows):
     """The entries of one monitor, and (HIP backend) its device tables: one
     per set of field arrays seen, so the table is built once per monitor and
     ping-pong state, not once per call."""
@@ -90,12 +100,6 @@ class DftEntries:
         self.rows.append(e)
         self.tables.clear()
         return e
-
-    def __iter__(self):
-        return iter(self.rows)
-
-    def __len__(self):
-        return len(self.rows)
 
 
 # ------------------------------------------------------------------ flux terms
@@ -127,6 +131,20 @@ class FluxOperand:
                     self.first[a], last, a, tuple(self.acc.shape[2:]))
         return None
 
+    def centre(self, extent) -> torch.Tensor:
+        """(K, 2) + ``extent`` float64: the face-centre average of the 1, 2 or
+        4 samples around every cell of a face (the torch backend's ops)."""
+        acc, cnt = None, 0
+        for ox in ((0, 1) if self.avg[0] else (0,)):
+            for oy in ((0, 1) if self.avg[1] else (0,)):
+                for oz in ((0, 1) if self.avg[2] else (0,)):
+                    o = (ox, oy, oz)
+                    sl = tuple(slice(self.first[a] + o[a], self.first[a] + o[a] + extent[a]) for a in range(3))
+                    v = self.acc[(slice(None), slice(None)) + sl].to(torch.float64)
+                    acc = v if acc is None else acc + v
+                    cnt += 1
+        return acc / cnt
+
 
 class FluxTerm:
     """``sign * sum over the face cells of (Re e Re h + Im e Im h)`` added to
@@ -146,7 +164,7 @@ class FluxTerm:
         return any(v <= 0 for v in self.extent)
 
 
-class FluxTerms:
+class FluxTerms(_Rows):
     """The products of one flux monitor (``ops.dft_flux``) and, on the HIP
     backend, its cached device table."""
 
@@ -161,12 +179,6 @@ class FluxTerms:
         self.rows.append(term)
         self.table = None
         return term
-
-    def __iter__(self):
-        return iter(self.rows)
-
-    def __len__(self):
-        return len(self.rows)
 
 
 # ------------------------------------------------------------- far-field terms
@@ -201,7 +213,7 @@ class FarTerm:
         return any(v <= 0 for v in self.extent)
 
 
-class FarTerms:
+class FarTerms(_Rows):
     """The currents of one far-field monitor (``ops.dft_farfield``) at ``k``
     wavelengths on a grid of step ``dx`` and, on the HIP backend, its cached
     device table."""
@@ -215,9 +227,3 @@ class FarTerms:
         self.rows.append(term)
         self.table = None
         return term
-
-    def __iter__(self):
-        return iter(self.rows)
-
-    def __len__(self):
-        return len(self.rows)

@@ -12,7 +12,7 @@ from typing import List, Tuple
 
 import torch
 
-from .dft import box_empty
+from .dft import _Rows, box_empty
 
 Box = Tuple[Tuple[int, int, int], Tuple[int, int, int]]
 
@@ -35,7 +35,7 @@ class EnergyEntry:
         return box_empty(self.box)
 
 
-class EnergyEntries:
+class EnergyEntries(_Rows):
     """The entries of one monitor with ``R`` result rows and (HIP backend) its
     device tables: one per set of field arrays seen, so the table is built
     once per monitor and ping-pong state, not once per call."""
@@ -52,9 +52,3 @@ class EnergyEntries:
         self.rows.append(e)
         self.tables.clear()
         return e
-
-    def __iter__(self):
-        return iter(self.rows)
-
-    def __len__(self):
-        return len(self.rows)

@@ -588,18 +588,6 @@ class TorchOps:
         dev = terms.rows[0].e.acc.device if len(terms) else "cpu"
         out = torch.zeros((terms.faces, terms.k), dtype=torch.float64, device=dev)
 
-        def centre(op, ext):
-            acc, cnt = None, 0
-            for ox in ((0, 1) if op.avg[0] else (0,)):
-                for oy in ((0, 1) if op.avg[1] else (0,)):
-                    for oz in ((0, 1) if op.avg[2] else (0,)):
-                        o = (ox, oy, oz)
-                        sl = tuple(slice(op.first[a] + o[a], op.first[a] + o[a] + ext[a]) for a in range(3))
-                        v = op.acc[(slice(None), slice(None)) + sl].to(torch.float64)
-                        acc = v if acc is None else acc + v
-                        cnt += 1
-            return acc / cnt
-
         for t in terms:
             for op in (t.e, t.h):
                 why = None if t.empty else op.reach_error(t.extent, terms.k)
@@ -607,7 +595,7 @@ class TorchOps:
                     raise ValueError("dft_flux: " + why)
             if t.empty:
                 continue
-            e, h = centre(t.e, t.extent), centre(t.h, t.extent)
+            e, h = t.e.centre(t.extent), t.h.centre(t.extent)
             out[t.face] += t.sign * (e[:, 0] * h[:, 0] + e[:, 1] * h[:, 1]).sum(dim=(1, 2, 3))
         return out
 
@@ -635,16 +623,7 @@ class TorchOps:
             why = t.operand.reach_error(t.extent, terms.k)
             if why:
                 raise ValueError("dft_farfield: " + why)
-            op, acc, cnt = t.operand, None, 0
-            for ox in ((0, 1) if op.avg[0] else (0,)):
-                for oy in ((0, 1) if op.avg[1] else (0,)):
-                    for oz in ((0, 1) if op.avg[2] else (0,)):
-                        o = (ox, oy, oz)
-                        sl = tuple(slice(op.first[a] + o[a], op.first[a] + o[a] + t.extent[a]) for a in range(3))
-                        v = op.acc[(slice(None), slice(None)) + sl].to(torch.float64)
-                        acc = v if acc is None else acc + v
-                        cnt += 1
-            acc = acc / cnt
+            acc = t.operand.centre(t.extent)
             val = torch.complex(acc[:, 0], acc[:, 1]).reshape(terms.k, -1)          # (K, C)
             pos = torch.stack(torch.meshgrid(*[t.pos0[a] + terms.dx * torch.arange(t.extent[a], dtype=torch.float64,
                                                                                    device=dev) for a in range(3)],
