@@ -876,6 +876,8 @@ class HipOps(HipMonitorOps):
         tail = (c_int(T), c_int(min(einc.numel(), reach)), c_int(sets.n_e), c_int(sets.n_h), _ptr(sets.i0),
                 _ptr(sets.w0), _ptr(sets.w1), _ptr(sets.c), _ptr(g), _stream())
         if dry:
+            # (tests/test_tb_variants_gpu.py drops this cache by its name to start a dry pass from
+            # zeroed scratch lines)
             scr = sets.__dict__.setdefault("scratch_lines", {})
             sl = scr.get(slot)
             if sl is None or sl[0].numel() != einc.numel():
@@ -942,6 +944,9 @@ class HipOps(HipMonitorOps):
             src = [i, j, k0, E.index(comp), k1]
             v8[:steps] = [float(v) for v in vals[:steps]]
         arr = lambda names, f: (c_vp * 3)(*[f[c].data_ptr() for c in names])
+        # the launcher picks the tile shape from the library's global: push this backend's knob
+        # (as tb_drude_step does), or the pass runs whatever shape the last plain tb_step left
+        self.lib.fdtd_set_tb_mr_shape(c_int(self.tb_mr_shape))
         rc = self.lib.fdtd_tb3d_amp_f32(
             arr(E, fin), arr(H, fin), arr(E, fout), arr(H, fout), c_double(cbv), c_double(dbv), c_int(shape[0]),
             c_int(shape[1]), c_int(shape[2]), _box_arr([boxes[c] for c in E + H]), _box_arr([obox]),

@@ -172,10 +172,12 @@ class TorchOps:
                 obox: Box, cb: Dict[str, Coef], steps: int, sources=None, tfsf=None) -> None:
         """Reference semantics of the temporally blocked kernel: ``steps``
         fused steps on the update boxes (reads outside the arrays count as
-        zero, like the kernel's unloaded rows), then only ``obox`` ∩ each
-        component's box is written to ``fout``.  ``tfsf`` = (TfsfSets, g
-        table, first level): each level adds coef * g to the set's target
-        cells after the curl update (the kernel adds g to the curl)."""
+        zero, like the kernel's unloaded rows), then ``obox`` is written to
+        ``fout`` for every component (cells outside a component's update box
+        with their input value: the kernels store whole output boxes).
+        ``tfsf`` = (TfsfSets, g table, first level): each level adds coef * g
+        to the set's target cells after the curl update (the kernel adds g to
+        the curl)."""
         pad = {c: torch.nn.functional.pad(fin[c], (1, 1, 1, 1, 1, 1)) for c in fin}
         shifted = {c: ((b[0][0] + 1, b[0][1] + 1, b[0][2] + 1), (b[1][0] + 1, b[1][1] + 1, b[1][2] + 1))
                    for c, b in boxes.items()}
@@ -196,11 +198,12 @@ class TorchOps:
             if tfsf is not None:
                 self._tfsf_level(nxt, tfsf, l, "H", shifted, cbp)
             cur = nxt
-        for c, b in boxes.items():
-            ob = box_intersect_(b, obox)
-            if not _empty(ob):
-                sl = box_slices(ob)
-                sp = tuple(slice(s.start + 1, s.stop + 1) for s in sl)
+        # the whole output box of every component, like the kernels: a cell
+        # outside its component's update box carries its input value
+        if not _empty(obox):
+            sl = box_slices(obox)
+            sp = tuple(slice(s.start + 1, s.stop + 1) for s in sl)
+            for c in boxes:
                 fout[c][sl] = cur[c][sp]
 
     tb_drude_max_steps = 5
@@ -246,11 +249,12 @@ class TorchOps:
                 nxt[comp][tuple(i + 1 for i in idx)] = val
             self.curl_update("H", h, nxt, nxt, cbp)
             cur = nxt
-        for c, b in boxes.items():
-            ob = box_intersect_(b, obox)
-            if not _empty(ob):
-                sl = box_slices(ob)
-                sp = tuple(slice(s.start + 1, s.stop + 1) for s in sl)
+        # the whole output box of every component, like the kernels: a cell
+        # outside its component's update box carries its input value
+        if not _empty(obox):
+            sl = box_slices(obox)
+            sp = tuple(slice(s.start + 1, s.stop + 1) for s in sl)
+            for c in boxes:
                 fout[c][sl] = cur[c][sp]
         ob = box_intersect_(B, obox)
         if not _empty(ob):
