@@ -128,6 +128,10 @@ class TorchOps:
             nxt = {c: F[c].clone() for c in F}
             src = None if vals is None else ("Ez", (int(src_i), 0, 0), float(vals[s]))
             self.fused_step(F, nxt, boxes, cb, src)
+            if src is not None:
+                # a hard source stays in the field wherever it sits (fused_step stores the E box
+                # only: on a cell outside it, cell 0, the value would reach Hy and then be lost)
+                nxt["Ez"][src[1]] = src[2]
             for c in F:
                 F[c].copy_(nxt[c])
 
