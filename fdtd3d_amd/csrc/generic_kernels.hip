@@ -169,6 +169,13 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_scattered(const T* __restrict__ f, T* __restrict__ out,
                                                    const T* __restrict__ line, int nline, int nx, int ny, int nz,
                                                    ScatGeom g) {
+  // Every operation below is rounded on its own, like the torch expression of
+  // io/dump.py: with FMA contraction the position d differs from it by an ulp,
+  // which the slope of the line turns into an error far above fp64 rounding
+  // (and the interpolation index can flip).  The __dmul_rn / __dadd_rn
+  // intrinsics do not prevent that: they are plain operators to the compiler
+  // and were contracted like any other (tests/test_aux_gpu.py test_scattered).
+#pragma clang fp contract(off)
   const long long n = (long long)nx * ny * nz;
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
     const int k = (int)(t % nz);
@@ -185,16 +192,15 @@ __global__ __launch_bounds__(256) void k_scattered(const T* __restrict__ f, T* _
       out[t] = v;
       continue;
     }
-    // explicitly rounded operations (no FMA contraction): the same value as
-    // the torch expression, so the interpolation index never flips
-    double d = __dadd_rn(__dadd_rn(__dmul_rn(x - g.zero[0], g.dir[0]), __dmul_rn(y - g.zero[1], g.dir[1])),
-                         __dmul_rn(z - g.zero[2], g.dir[2]));
+    // the same value as the torch expression, so the interpolation index never flips
+    double d = ((x - g.zero[0]) * g.dir[0] + (y - g.zero[1]) * g.dir[1]) + (z - g.zero[2]) * g.dir[2];
     d = d - g.shift;
     long long i0 = (long long)floor(d);
     i0 = i0 < 0 ? 0 : (i0 > nline - 2 ? nline - 2 : i0);
     const double w1 = d - (double)i0;
-    const double li = __dadd_rn(__dmul_rn(1.0 - w1, (double)line[i0]), __dmul_rn(w1, (double)line[i0 + 1]));
-    out[t] = v - (T)__dmul_rn(li, g.proj);
+    const double li = (1.0 - w1) * (double)line[i0] + w1 * (double)line[i0 + 1];
+    const T inc = (T)(li * g.proj);
+    out[t] = v - inc;
   }
 }
 

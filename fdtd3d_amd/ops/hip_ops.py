@@ -620,6 +620,13 @@ class HipOps(HipMonitorOps):
         self.launches += 1
 
     # ------------------------------------------------------------------ halo
+    def _check_buffer(self, buf: torch.Tensor, like: torch.Tensor, what: str) -> None:
+        """A message buffer: the fields' device, this backend's dtype,
+        contiguous (the kernels address it as a flat array of field elements)."""
+        if buf.device != like.device or buf.dtype != self.dtype or not buf.is_contiguous():
+            raise HipError("%s buffer on %s/%s (contiguous=%s), need %s/%s contiguous"
+                           % (what, buf.device, buf.dtype, buf.is_contiguous(), like.device, self.dtype))
+
     def pack(self, tensors: Sequence[torch.Tensor], box: Box, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         shape = tuple(tensors[0].shape)
         n = 1
@@ -629,6 +636,7 @@ class HipOps(HipMonitorOps):
                 raise HipError("pack box %s outside %s" % (box, shape))
         if out is None:
             out = torch.empty(n * len(tensors), dtype=self.dtype, device=self.device)
+        self._check_buffer(out, tensors[0], "pack")
         if out.numel() < n * len(tensors):
             raise HipError("pack buffer too small")
         for t in tensors:
@@ -661,6 +669,7 @@ class HipOps(HipMonitorOps):
             n *= max(0, box[1][d] - box[0][d])
             if box[0][d] < 0 or box[1][d] > shape[d]:
                 raise HipError("unpack box %s outside %s" % (box, shape))
+        self._check_buffer(buf, tensors[0], "unpack")
         if buf.numel() < n * len(tensors):
             raise HipError("unpack buffer too small")
         for t in tensors:
@@ -699,6 +708,12 @@ class HipOps(HipMonitorOps):
         return s
 
     def maxabs(self, t: torch.Tensor, box: Box) -> float:
+        """max |t| over ``box`` as the float32 the kernel reduces in
+        (aux_kernels.hip k_box_maxabs): every value is cast to float first, so
+        the result is ``float32(max |t[box]|)`` exactly.  NaN anywhere in the
+        box gives ``inf``.  An fp64 value that is finite but above FLT_MAX
+        also gives ``inf`` -- ``YeeScheme.check_finite`` reports such a field as
+        non-finite -- and one below the smallest fp32 subnormal gives 0."""
         if _empty(box):
             return 0.0
         self._check_tensor(t)
@@ -738,6 +753,9 @@ class HipOps(HipMonitorOps):
         """Amplitude update of several components in one launch; the number
         of changed cells is ADDED to the device int32 ``counter`` (one
         element) -- no host synchronisation."""
+        if not (1 <= len(fields) <= 6) or len(amps) != len(fields) or len(boxes) != len(fields):
+            raise HipError("amplitude_update_many: 1..6 fields with one amplitude array and one box each, got "
+                           "%d / %d / %d" % (len(fields), len(amps), len(boxes)))
         shape = tuple(fields[0].shape)
         xs = self._check_amp(amps, shape)
         for f in fields:

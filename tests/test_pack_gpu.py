@@ -1,6 +1,8 @@
 """Halo pack / unpack kernels (aux_kernels.hip box_pack / box_unpack): the
 16-byte vector path (aligned rows) and the element-wise fallback (unaligned
-z start, odd z span, unaligned buffer) against torch slicing, fp32 and fp64."""
+z start, odd z span, unaligned buffer) against torch slicing, fp32 and fp64.
+The grid-stride loop, the 8-component and grid.z limits and misaligned field
+bases, which this array never reaches: tests/test_aux_gpu.py."""
 import pytest
 import torch
 

@@ -1,6 +1,8 @@
 """Scattered-field kernel (generic_kernels.hip k_scattered, used for the
 --save-scattered-field dumps) against the torch expression of io/dump.py on
-the same fields: 3D (oblique incidence, fp32 / fp64) and TMz."""
+the same fields: 3D (oblique incidence, fp32 / fp64) and TMz.
+Per-cell bounds against an fp64 CPU oracle on live fields, a non-zero rank
+origin, border cells, the index clamps and two sweeps: tests/test_aux_gpu.py."""
 import pytest
 import torch
 
