@@ -80,15 +80,31 @@ int fdtd_fused3d_v4_f32(const float* const* ein, const float* const* hin, float*
                         int nz, const int* boxes, int xchunk, long long src_off, int src_comp, double src_val,
                         void* s);
 
+// Tile options of one blocked 3D pass (yee3d_tb.hip, yee3d_tb64.hip): every
+// fdtd_tb3d_* entry point takes them as ``opts``; a null pointer means the
+// defaults, a value outside a field's range its default
+struct FdtdTbOpts {
+  int vec;       // single-row kernel, lane width: 0 = automatic (4 for T <= 2, 2 above), 2, 4
+  int rows;      // single-row kernel, rows per wave: 0 = automatic (1), 1, 2
+  int xcd;       // single-row kernel, XCD-aware tile order: 0 (default) / 1
+  int mrows;     // rows per wave of a plain fp32 pass: 0 = automatic, 1 = the single-row kernel, 2 = multi-row
+  int variant;   // multi-row kernel: bit 0 deferred stores, bit 1 two planes prefetched, bit 2 XCD-contiguous
+                 // tile order, bit 3 no interior fast path; default 4
+  int mr_shape;  // multi-row tiles: 0 = 16 waves x 2 rows, 1 = 8 waves x 4 rows, 2 = 8 waves x 2 rows
+  int dr_shape;  // Drude variant tiles: 0 = 8 waves x 2 rows, 1 = 16 waves x 1 row
+  int half64;    // fp64 tiles: 1 = two rows of 32 lanes per wave (default), 0 = one row of 64 lanes
+};
+int fdtd_tb_opts_size();  // sizeof(FdtdTbOpts) (ABI check)
 int fdtd_tb3d_v4_f32(const float* const* ein, const float* const* hin, float* const* eout, float* const* hout,
                      const float* const* cbs, const float* const* dbs, double cb, double db, int nx, int ny, int nz,
                      const int* boxes, const int* obox, int xchunk, int steps, const int* src, const double* src_vals,
-                     void* stream);
+                     const FdtdTbOpts* opts, void* stream);
 int fdtd_tb_max_steps();
 int fdtd_tb3d_ext_f32(const float* const* ein, const float* const* hin, float* const* eout, float* const* hout,
                       const void* ce4, const int* ebox, const void* ch4, const int* hbox, double cb, double db,
                       int nx, int ny, int nz, const int* boxes, const int* obox, int xchunk, int steps,
-                      const int* src, const double* src_vals, const void* tf, const float* gtab, void* stream);
+                      const int* src, const double* src_vals, const void* tf, const float* gtab,
+                      const FdtdTbOpts* opts, void* stream);
 int fdtd_box_pack_f32(float* const* fields, float* buf, int ncomp, int ny, int nz, const int* box, void* s);
 int fdtd_box_pack_f64(double* const* fields, double* buf, int ncomp, int ny, int nz, const int* box, void* s);
 int fdtd_box_unpack_f32(float* const* fields, const float* buf, int ncomp, int ny, int nz, const int* box, void* s);
@@ -98,11 +114,11 @@ int fdtd_box_xfer_f64(double* const* src, double* const* dst, int ncomp, int ny,
 int fdtd_tb3d_amp_f32(const float* const* ein, const float* const* hin, float* const* eout, float* const* hout,
                       double cb, double db, int nx, int ny, int nz, const int* boxes, const int* obox, int xchunk,
                       int steps, const int* src, const double* src_vals, float* const* amp, const int* aboxes,
-                      double accuracy, unsigned* counts, void* stream);
+                      double accuracy, unsigned* counts, const FdtdTbOpts* opts, void* stream);
 int fdtd_tb3d_drude_f32(const float* const* ein, const float* const* hin, float* const* eout, float* const* hout,
                         double cb, double db, int nx, int ny, int nz, const int* boxes, const int* obox, int xchunk,
                         int steps, const int* src, const double* src_vals, const int* bbox, void* const* sin,
-                        void* const* sout, const void* lut, int nid, double cbd, void* stream);
+                        void* const* sout, const void* lut, int nid, double cbd, const FdtdTbOpts* opts, void* stream);
 int fdtd_tfdev_size();
 int fdtd_tfsf_pass_f32(float* einc, float* hinc, int n, double ce, double ch, const double* src_vals, int steps,
                        int reach, int nE, int nH, const int* I0, const float* W0, const float* W1, const float* C,
@@ -113,11 +129,12 @@ int fdtd_tfsf_table_f32(const float* esrc, const float* hsrc, float* einc, float
 int fdtd_tb3d_f64(const double* const* ein, const double* const* hin, double* const* eout, double* const* hout,
                   const double* const* cbs, const double* const* dbs, double cb, double db, int nx, int ny, int nz,
                   const int* boxes, const int* obox, int xchunk, int steps, const int* src, const double* src_vals,
-                  void* stream);
+                  const FdtdTbOpts* opts, void* stream);
 int fdtd_tb3d_drude_f64(const double* const* ein, const double* const* hin, double* const* eout, double* const* hout,
                         double cb, double db, int nx, int ny, int nz, const int* boxes, const int* obox, int xchunk,
                         int steps, const int* src, const double* src_vals, const int* bbox, void* const* sin,
-                        void* const* sout, const double* lut, int nid, double cbd, void* stream);
+                        void* const* sout, const double* lut, int nid, double cbd, const FdtdTbOpts* opts,
+                        void* stream);
 int fdtd_tfsf_pass_f64(double* einc, double* hinc, int n, double ce, double ch, const double* src_vals, int steps,
                        int reach, int nE, int nH, const int* I0, const double* W0, const double* W1, const double* C,
                        double* gtab, void* stream);
@@ -127,9 +144,8 @@ int fdtd_tfsf_table_f64(const double* esrc, const double* hsrc, double* einc, do
 int fdtd_tb3d_tf_f64(const double* const* ein, const double* const* hin, double* const* eout, double* const* hout,
                      const double* const* cbs, const double* const* dbs, double cb, double db, int nx, int ny, int nz,
                      const int* boxes, const int* obox, int xchunk, int steps, const int* src,
-                     const double* src_vals, const void* tf, const double* gtab, void* stream);
+                     const double* src_vals, const void* tf, const double* gtab, const FdtdTbOpts* opts, void* stream);
 int fdtd_tb64_max_steps();
-void fdtd_set_tb64_shape(int half);
 int fdtd_tb2d_f32(int mode, const float* const* ein, const float* const* hin, float* const* eout, float* const* hout,
                   const float* const* cs, double cb, double db, int nx, int ny, const int* boxes, const int* obox,
                   int xchunk, int steps, const int* src, const double* src_vals, void* stream);

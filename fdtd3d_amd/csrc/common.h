@@ -7,6 +7,7 @@
 #pragma once
 
 #include <cstdlib>
+#include <type_traits>
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,6 +48,27 @@ static inline Box3 make_box(const int* lohi) {
 }
 
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
+
+// What every blocked 3D entry point reads first (yee3d_tb.hip, yee3d_tb64.hip):
+// the six update boxes (Ex Ey Ez Hx Hy Hz), the output box and the hard
+// source's value at each of the `steps` levels (SV = TbSrc / TbSrc64; all 0
+// without a source, src[3] < 0).  False: the output box is empty, nothing to
+// launch.
+template <typename SV>
+struct TbPass {
+  Box3 b[6];
+  Box3 O;
+  SV sv;
+};
+template <typename SV>
+static inline bool tb_pass(TbPass<SV>& p, const int* boxes, const int* obox, int steps, const int* src,
+                           const double* src_vals) {
+  for (int n = 0; n < 6; ++n) p.b[n] = make_box(boxes + 6 * n);
+  p.O = make_box(obox);
+  typedef typename std::remove_reference<decltype(p.sv.v[0])>::type R;
+  for (int l = 0; l < 8; ++l) p.sv.v[l] = (src[3] >= 0 && l < steps) ? (R)src_vals[l] : (R)0;
+  return !box_empty(p.O);
+}
 
 // x planes per workgroup of the x-streaming split kernels: 16 (measured best
 // on full grids), halved while the launch would hold fewer than 2048

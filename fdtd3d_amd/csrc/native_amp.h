@@ -110,7 +110,7 @@ struct AmpMode {
             double vals[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             for (int l = 0; l < k; ++l) vals[l] = src_val(t + l);
             K_OK(fdtd_tb3d_amp_f32(ei, hi, eo, ho, cb, db, N[0], N[1], N[2], boxes, ob, 0, k, src5, vals, aa, ab,
-                                   0.001, CNT.p + q, st));
+                                   0.001, CNT.p + q, nullptr, st));
             for (int c = 0; c < 6; ++c) std::swap(F[c].p, G[c].p);
             for (int c = 0; c < 6; ++c) af[c] = F[c].p;
             q += k;

@@ -107,7 +107,8 @@ int fused(const double* const* ei, const double* const* hi, double* const* eo, d
           const int* bx, long long so, int sc, double sv, void* s, bool) {
   return fdtd_fused3d_f64(ei, hi, eo, ho, cbs, dbs, cb, db, nx, ny, nz, bx, 0, so, sc, sv, s);
 }
-// temporally blocked pass (fp32: yee3d_tb.hip, fp64: yee3d_tb64.hip)
+// temporally blocked pass (fp32: yee3d_tb.hip, fp64: yee3d_tb64.hip), with the library's default tile options
+// (a null FdtdTbOpts)
 // fp32: a sparse float4 box of the E coefficients (ce4 over ebox, scalar cb
 // elsewhere, scalar db) takes the multi-row kernel; otherwise per-kind arrays
 int tb3d(const float* const* ei, const float* const* hi, float* const* eo, float* const* ho, const float* const* cbs,
@@ -119,29 +120,30 @@ int tb3d(const float* const* ei, const float* const* hi, float* const* eo, float
   if (ce4) {
     const int none[6] = {0, 0, 0, 0, 0, 0};
     return fdtd_tb3d_ext_f32(ei, hi, eo, ho, ce4, ebox, nullptr, none, cb, db, nx, ny, nz, bx, ob, 0, T, src, vals,
-                             nullptr, nullptr, s);
+                             nullptr, nullptr, nullptr, s);
   }
-  return fdtd_tb3d_v4_f32(ei, hi, eo, ho, cbs, dbs, cb, db, nx, ny, nz, bx, ob, 0, T, src, vals, s);
+  return fdtd_tb3d_v4_f32(ei, hi, eo, ho, cbs, dbs, cb, db, nx, ny, nz, bx, ob, 0, T, src, vals, nullptr, s);
 }
 int tb3d(const double* const* ei, const double* const* hi, double* const* eo, double* const* ho,
          const double* const* cbs, const double* const* dbs, double cb, double db, int nx, int ny, int nz,
          const int* bx, int T, const int* src, const double* vals, void* s, const void* = nullptr,
          const int* = nullptr, const int* obox = nullptr) {
   const int whole[6] = {0, 0, 0, nx, ny, nz};
-  return fdtd_tb3d_f64(ei, hi, eo, ho, cbs, dbs, cb, db, nx, ny, nz, bx, obox ? obox : whole, 0, T, src, vals, s);
+  return fdtd_tb3d_f64(ei, hi, eo, ho, cbs, dbs, cb, db, nx, ny, nz, bx, obox ? obox : whole, 0, T, src, vals,
+                       nullptr, s);
 }
 // the Drude pass of a hybrid pass (fp32: tb3d_mr.h DrDev, fp64: yee3d_tb64.hip DrDev64)
 int drude3d(const float* const* ei, const float* const* hi, float* const* eo, float* const* ho, double cb, double db,
             int nx, int ny, int nz, const int* bx, const int* ob, int T, const int* src, const double* vals,
             const int* bb, void* const* sin, void* const* sout, const float* lut, int nid, double cbd, void* s) {
   return fdtd_tb3d_drude_f32(ei, hi, eo, ho, cb, db, nx, ny, nz, bx, ob, 0, T, src, vals, bb, sin, sout, lut, nid,
-                             cbd, s);
+                             cbd, nullptr, s);
 }
 int drude3d(const double* const* ei, const double* const* hi, double* const* eo, double* const* ho, double cb,
             double db, int nx, int ny, int nz, const int* bx, const int* ob, int T, const int* src, const double* vals,
             const int* bb, void* const* sin, void* const* sout, const double* lut, int nid, double cbd, void* s) {
   return fdtd_tb3d_drude_f64(ei, hi, eo, ho, cb, db, nx, ny, nz, bx, ob, 0, T, src, vals, bb, sin, sout, lut, nid,
-                             cbd, s);
+                             cbd, nullptr, s);
 }
 // CPML half steps with the psi terms folded in (yee3d_cpml.hip, 4-cell z lanes)
 int cpml_e3d(float* const* F, const float* const* C, double cb, int nx, int ny, int nz, const int* bx,

@@ -429,10 +429,10 @@ void MultiRun<T>::rank_pass(XRank<T>& q, int t, int k) {
     if (ob[3] <= ob[0] || ob[4] <= ob[1] || ob[5] <= ob[2]) continue;
     if constexpr (sizeof(T) == 4)
       K_OK(fdtd_tb3d_v4_f32(ei, hi, eo, ho, cbs, dbs, percell ? 1.0 : cb, db, q.n[0], q.n[1], q.n[2], q.boxes, ob, 0,
-                            k, src, vals, q.st));
+                            k, src, vals, nullptr, q.st));
     else
       K_OK(fdtd_tb3d_f64(ei, hi, eo, ho, cbs, dbs, percell ? 1.0 : cb, db, q.n[0], q.n[1], q.n[2], q.boxes, ob, 0, k,
-                         src, vals, q.st));
+                         src, vals, nullptr, q.st));
   }
   if (!first && q.outs.size() == 1) HIP_OK(hipStreamWaitEvent(q.st, q.copied, 0));  // a lone rank
   for (int c = 0; c < 6; ++c) std::swap(q.F[c].p, q.G[c].p);

@@ -1,12 +1,15 @@
 // Multi-row temporally blocked fp32 3D Yee kernel (k_tb3d_mr) and its
 // launcher (yee3d_tb.hip holds the host API): plain, sparse per-cell
-// coefficient and TF/SF variants.
+// coefficient and TF/SF variants.  The tile options of a pass (FdtdTbOpts,
+// capi.h) reach the launcher as an argument: nothing here is process state
+// but the constants read once from the environment.
 #pragma once
 
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
+#include "capi.h"
 #include "common.h"
 #include "tfsf_dev.h"
 
@@ -1006,31 +1009,62 @@ __global__ __launch_bounds__(64 * NW) void k_tb3d_mr(
 }
 
 
-// host-side knobs of the multi-row launches (defined in yee3d_tb.hip)
-extern int g_tb_mr_noallin;
-extern int g_tb_mr_xcd;
-extern int g_tb_variant;
-int tb_patch_bits();
+// Tile options of a pass as the launchers read them: FdtdTbOpts (capi.h)
+// with every field clamped to its range -- a value outside it takes the
+// field's default --, a null pointer = the defaults
+inline FdtdTbOpts tb_opts(const FdtdTbOpts* p) {
+  FdtdTbOpts o = {/*vec*/ 0, /*rows*/ 0, /*xcd*/ 0, /*mrows*/ 0, /*variant*/ 4, /*mr_shape*/ 0, /*dr_shape*/ 0,
+                  /*half64*/ 1};
+  if (!p) return o;
+  o.vec = (p->vec == 2 || p->vec == 4) ? p->vec : 0;
+  o.rows = (p->rows == 1 || p->rows == 2) ? p->rows : 0;
+  o.xcd = p->xcd ? 1 : 0;
+  o.mrows = (p->mrows == 1 || p->mrows == 2) ? p->mrows : 0;
+  o.variant = p->variant & 15;
+  o.mr_shape = (p->mr_shape == 1 || p->mr_shape == 2) ? p->mr_shape : 0;
+  o.dr_shape = p->dr_shape == 1 ? 1 : 0;
+  o.half64 = p->half64 ? 1 : 0;
+  return o;
+}
 
+// patch order of the XCD-contiguous tile run (k_tb3d_mr): (pz << 8) | (py << 16),
+// 0 = z fastest; FDTD3D_TB_PATCH="PZxPY" (e.g. 4x8), read at first use
+inline int tb_patch_bits() {
+  static const int bits = [] {
+    const char* e = getenv("FDTD3D_TB_PATCH");
+    int pz = 0, py = 0;
+    if (e && sscanf(e, "%dx%d", &pz, &py) == 2 && pz > 0 && py > 0 && pz < 256 && py < 256)
+      return (pz << 8) | (py << 16);
+    return 0;
+  }();
+  return bits;
+}
+
+// ``o`` (tb_opts): variant bit 0 deferred stores, bit 1 two planes prefetched
+// (both: uniform media only), bit 2 XCD-contiguous tile order, z fastest
+// (-16..20% HBM reads), bit 3 the masked loop everywhere (no interior fast
+// path: an A/B knob)
 template <int T, int V, int R, int FX, int NW = TBW>
-int launch_tb_mr(const float* const* ein, const float* const* hin, float* const* eout, float* const* hout,
-                 const float4* ce4, const float4* ch4, const Box3& BE, const Box3& BH, float cb, float db, int nx,
-                 int ny, int nz, const Box3* b, const Box3& O, int xchunk, const int* src, const TbSrc& sv,
-                 const TfDev* tf, const float* gtab, const AmpDev& amp, hipStream_t s, const DrDev& dr = DrDev{}) {
+int launch_tb_mr(const FdtdTbOpts& o, const float* const* ein, const float* const* hin, float* const* eout,
+                 float* const* hout, const float4* ce4, const float4* ch4, const Box3& BE, const Box3& BH, float cb,
+                 float db, int nx, int ny, int nz, const Box3* b, const Box3& O, int xchunk, const int* src,
+                 const TbSrc& sv, const TfDev* tf, const float* gtab, const AmpDev& amp, hipStream_t s,
+                 const DrDev& dr = DrDev{}) {
   constexpr int HL = (T + V - 1) / V;
   constexpr int TBZ = (64 - 2 * HL) * V;
   dim3 grid(cdiv(O.hi[2] - (O.lo[2] & ~(V - 1)), TBZ), cdiv(O.hi[1] - O.lo[1], NW * R - 2 * T),
             cdiv(O.hi[0] - O.lo[0], xchunk));
+  const int noallin = (o.variant >> 3) & 1;
+  const int swz = (o.variant & 4) ? (1 | (noallin << 1) | tb_patch_bits()) : (noallin << 1);
 #define MR_LAUNCH(PFD, DEFER)                                                                                 \
   k_tb3d_mr<T, V, R, FX, PFD, DEFER, NW><<<grid, dim3(64, NW), 0, s>>>(                                     \
       ein[0], ein[1], ein[2], hin[0], hin[1], hin[2], eout[0], eout[1], eout[2], hout[0], hout[1], hout[2], \
       ce4, ch4, BE, BH, cb, db, nx, ny, nz, b[0], b[1], b[2], b[3], b[4], b[5],                             \
-      O, xchunk, src[0], src[1], src[2], src[3], sv,                                                       \
-      g_tb_mr_xcd ? (1 | (g_tb_mr_noallin << 1) | tb_patch_bits()) : (g_tb_mr_noallin << 1), tf, gtab, amp, dr)
+      O, xchunk, src[0], src[1], src[2], src[3], sv, swz, tf, gtab, amp, dr)
   if constexpr (FX != 0) {
     MR_LAUNCH(1, false);  // tuning variants: uniform media only
   } else {
-    switch (g_tb_variant & 3) {
+    switch (o.variant & 3) {
       case 0: MR_LAUNCH(1, false); break;
       case 1: MR_LAUNCH(1, true); break;
       case 2: MR_LAUNCH(2, false); break;

@@ -25,6 +25,11 @@
 // Update boxes (where each component may change) and the output box (cells
 // this launch stores) are separate: in a decomposed run the ghost layers are
 // updated redundantly at the inner levels but never stored.
+//
+// Which kernel and tile a pass takes is an argument of the pass: every entry
+// point below reads the caller's FdtdTbOpts (capi.h; null = the defaults) and
+// hands the clamped values (tb3d_mr.h tb_opts) down to its launcher.  The
+// library keeps no per-pass state between calls.
 
 #include <cstdio>
 #include <cstdlib>
@@ -33,25 +38,6 @@
 #include "common.h"
 
 #include "tb3d_mr.h"
-
-namespace tb3d {
-int g_tb_mr_noallin = 0;  // A/B knob: 1 = masked loop everywhere (no interior fast path)
-int g_tb_mr_xcd = 1;   // multi-row kernel: XCD-contiguous tile order, z fastest (-16..20% HBM reads)
-// patch order of the XCD-contiguous tile run (k_tb3d_mr): (pz << 8) | (py << 16),
-// 0 = z fastest; FDTD3D_TB_PATCH="PZxPY" (e.g. 4x8) at first use
-int g_tb_patch = -1;
-int tb_patch_bits() {
-  if (g_tb_patch < 0) {
-    g_tb_patch = 0;
-    const char* e = getenv("FDTD3D_TB_PATCH");
-    int pz = 0, py = 0;
-    if (e && sscanf(e, "%dx%d", &pz, &py) == 2 && pz > 0 && py > 0 && pz < 256 && py < 256)
-      g_tb_patch = (pz << 8) | (py << 16);
-  }
-  return g_tb_patch;
-}
-int g_tb_variant = 0;  // multi-row kernel: bit 0 deferred stores, bit 1 two planes prefetched
-}  // namespace tb3d
 
 namespace {
 
@@ -291,14 +277,11 @@ int pick_xchunk(long long tiles_yz, int nxo, int T, int wg_per_cu = 1) {
   return best;
 }
 
-int g_tb_vec = 0;   // 0: automatic (float4 lanes for T <= 2, float2 above), else 2 / 4
-int g_tb_rows = 0;  // rows per wave: 0 automatic (1), 1 / 2
-int g_tb_xcd = 0;   // XCD-aware tile order (measured: no gain, T=2 slower; off by default)
-
+// ``xcd``: XCD-aware tile order (measured: no gain, T=2 slower; off by default)
 template <int T, int V, int R, bool PERCELL>
 int launch_tb(const float* const* ein, const float* const* hin, float* const* eout, float* const* hout,
               const float* const* cbs, const float* const* dbs, float cb, float db, int nx, int ny, int nz,
-              const Box3* b, const Box3& O, int xchunk, const int* src, const TbSrc& sv, hipStream_t s) {
+              const Box3* b, const Box3& O, int xchunk, const int* src, const TbSrc& sv, hipStream_t s, int xcd) {
   constexpr int HL = (T + V - 1) / V;
   constexpr int TBZ = (64 / R - 2 * HL) * V;
   dim3 grid(cdiv(O.hi[2] - (O.lo[2] & ~(V - 1)), TBZ), cdiv(O.hi[1] - O.lo[1], TBW * R - 2 * T),
@@ -306,7 +289,7 @@ int launch_tb(const float* const* ein, const float* const* hin, float* const* eo
   k_tb3d<T, V, R, PERCELL><<<grid, dim3(64, TBW), 0, s>>>(
       ein[0], ein[1], ein[2], hin[0], hin[1], hin[2], eout[0], eout[1], eout[2], hout[0], hout[1], hout[2],
       cbs[0], cbs[1], cbs[2], dbs[0], dbs[1], dbs[2], cb, db, nx, ny, nz, b[0], b[1], b[2], b[3], b[4], b[5], O,
-      xchunk, src[0], src[1], src[2], src[3], sv, g_tb_xcd);
+      xchunk, src[0], src[1], src[2], src[3], sv, xcd);
   FDTD_RETURN_LAUNCH_STATUS();
 }
 
@@ -314,16 +297,16 @@ template <int T, int V, int R>
 int launch_tb_pc(bool pc, const float* const* ein, const float* const* hin, float* const* eout,
                  float* const* hout, const float* const* cbs, const float* const* dbs, float cb, float db, int nx,
                  int ny, int nz, const Box3* b, const Box3& O, int xchunk, const int* src, const TbSrc& sv,
-                 hipStream_t s) {
-  return pc ? launch_tb<T, V, R, true>(ein, hin, eout, hout, cbs, dbs, cb, db, nx, ny, nz, b, O, xchunk, src, sv, s)
+                 hipStream_t s, int xcd) {
+  return pc ? launch_tb<T, V, R, true>(ein, hin, eout, hout, cbs, dbs, cb, db, nx, ny, nz, b, O, xchunk, src, sv, s,
+                                       xcd)
             : launch_tb<T, V, R, false>(ein, hin, eout, hout, cbs, dbs, cb, db, nx, ny, nz, b, O, xchunk, src, sv,
-                                        s);
+                                        s, xcd);
 }
 
 // two rows per wave from 4 steps per pass on (T=4: 246-267k vs 247-260k
 // Mcells/s single-row at 1024^3; T=3: 162k vs 207k, so single-row below)
 constexpr int MR_AUTO_ROWS = 2;
-int g_tb_mrows = 0;  // rows per wave of the multi-row kernel: 0 automatic, 1 = single-row kernel, 2 / 4
 
 const int kNoBox[6] = {0, 0, 0, 0, 0, 0};
 // amplitude-mode tile shape (tuning): 0 = 16 waves x 2 rows, 2 = 8 waves x 2 rows
@@ -334,24 +317,25 @@ static int tb_amp_shape() {
   }();
   return v;
 }
-int g_tb_mr_shape = 0;  // plain multi-row kernel: 0 = 16 waves x 2 rows, 1 = 8 waves x 4 rows, 2 = 8 x 2
-int g_tb_dr_shape = 0;  // Drude variant: 0 = 8 waves x 2 rows, 1 = 16 waves x 1 row (both 16-row tiles)
 
-
-
+// the multi-row launch of feature set ``fx`` under the options ``o``: mr_shape
+// (plain and amplitude passes) 0 = 16 waves x 2 rows, 1 = 8 waves x 4 rows,
+// 2 = 8 x 2; dr_shape (Drude) 0 = 8 waves x 2 rows, 1 = 16 waves x 1 row
+// (both 16-row tiles)
 template <int T>
-int launch_tb_mr_sel(int fx, const float* const* ein, const float* const* hin, float* const* eout,
-                     float* const* hout, const float4* ce4, const float4* ch4, const Box3& BE, const Box3& BH,
-                     float cb, float db, int nx, int ny, int nz, const Box3* b, const Box3& O, int xchunk,
-                     const int* src, const TbSrc& sv, const TfDev* tf, const float* gtab, const AmpDev& amp,
-                     hipStream_t s, const DrDev& dr = DrDev{}) {
-#define MR_ARGS ein, hin, eout, hout, ce4, ch4, BE, BH, cb, db, nx, ny, nz, b, O, xchunk, src, sv, tf, gtab, amp, s, dr
+int launch_tb_mr_sel(int fx, const FdtdTbOpts& o, const float* const* ein, const float* const* hin,
+                     float* const* eout, float* const* hout, const float4* ce4, const float4* ch4, const Box3& BE,
+                     const Box3& BH, float cb, float db, int nx, int ny, int nz, const Box3* b, const Box3& O,
+                     int xchunk, const int* src, const TbSrc& sv, const TfDev* tf, const float* gtab,
+                     const AmpDev& amp, hipStream_t s, const DrDev& dr = DrDev{}) {
+#define MR_ARGS \
+  o, ein, hin, eout, hout, ce4, ch4, BE, BH, cb, db, nx, ny, nz, b, O, xchunk, src, sv, tf, gtab, amp, s, dr
   // amplitude mode: uniform media, T <= 3 (tb3d_mr.h AmpDev)
   // Drude box (tb3d_mr.h DrDev): 8 waves x 2 rows (16-row tiles, <= 256
   // VGPRs: the dispersive state of T - 1 levels rides in registers)
   if (fx == 16) {
     if constexpr (T <= 5) {
-      if (g_tb_dr_shape == 1) return launch_tb_mr<T, 1, 1, 16, 16>(MR_ARGS);
+      if (o.dr_shape == 1) return launch_tb_mr<T, 1, 1, 16, 16>(MR_ARGS);
       return launch_tb_mr<T, 1, 2, 16, 8>(MR_ARGS);
     }
     return (int)hipErrorInvalidValue;
@@ -361,7 +345,7 @@ int launch_tb_mr_sel(int fx, const float* const* ein, const float* const* hin, f
       // 16 waves x 2 rows; the 8 x 4 shape (tuning knob 1) needs 200-256 VGPRs;
       // 8 waves x 2 rows (FDTD3D_TB_AMP_SHAPE=2: 16-row tiles, up to 256
       // VGPRs -- the 16 x 2 form caps at 128 and spills)
-      if (g_tb_mr_shape == 1) return launch_tb_mr<T, 1, 4, 8, 8>(MR_ARGS);
+      if (o.mr_shape == 1) return launch_tb_mr<T, 1, 4, 8, 8>(MR_ARGS);
       if (tb_amp_shape() == 2) return launch_tb_mr<T, 1, 2, 8, 8>(MR_ARGS);
       return launch_tb_mr<T, 1, 2, 8>(MR_ARGS);
     }
@@ -385,33 +369,33 @@ int launch_tb_mr_sel(int fx, const float* const* ein, const float* const* hin, f
   // plain: 16 waves x 2 rows (4 waves / SIMD, <= 128 VGPRs) or 8 waves x 4
   // rows (2 waves / SIMD, <= 256 VGPRs: more rows of ILP per wave, half the
   // LDS row exchanges); both a 32-row tile
-  if (g_tb_mr_shape == 1) return launch_tb_mr<T, 1, 4, 0, 8>(MR_ARGS);
+  if (o.mr_shape == 1) return launch_tb_mr<T, 1, 4, 0, 8>(MR_ARGS);
   // 8 waves x 2 rows (16-row tiles, two workgroups per CU): thin y boxes, the
   // y shells of decomposed passes
   if constexpr (T <= 5)
-    if (g_tb_mr_shape == 2) return launch_tb_mr<T, 1, 2, 0, 8>(MR_ARGS);
+    if (o.mr_shape == 2) return launch_tb_mr<T, 1, 2, 0, 8>(MR_ARGS);
   return launch_tb_mr<T, 1, 2, 0>(MR_ARGS);
 #undef MR_ARGS
 }
 
 // automatic x chunk of a multi-row pass over output box O
-int tb_mr_xchunk(int fx, const Box3& O, int steps) {
+int tb_mr_xchunk(int fx, const FdtdTbOpts& o, const Box3& O, int steps) {
   const long long gz = cdiv(O.hi[2] - O.lo[2], 64 - 2 * steps);
   // (the Drude variant's tiles are 8 waves x 2 rows)
-  const bool amp16 = fx == 8 && g_tb_mr_shape != 1 && tb_amp_shape() == 2;
-  const bool rows16 = fx == 16 || amp16 || (fx == 0 && g_tb_mr_shape == 2 && steps <= 5);
+  const bool amp16 = fx == 8 && o.mr_shape != 1 && tb_amp_shape() == 2;
+  const bool rows16 = fx == 16 || amp16 || (fx == 0 && o.mr_shape == 2 && steps <= 5);
   const long long gy = cdiv(O.hi[1] - O.lo[1], (rows16 ? 16 : TBW * 2) - 2 * steps);
   // the 8-wave shapes fit two workgroups per CU
-  return pick_xchunk(gz * gy, O.hi[0] - O.lo[0], steps, ((fx == 0 && g_tb_mr_shape >= 1) || amp16) ? 2 : 1);
+  return pick_xchunk(gz * gy, O.hi[0] - O.lo[0], steps, ((fx == 0 && o.mr_shape >= 1) || amp16) ? 2 : 1);
 }
 
 // multi-row pass (scalar lanes, 2 rows per wave): uniform media, sparse
 // per-cell coefficients (fx bits 1 / 2), TF/SF corrections (fx bit 4)
-int tb_mr_dispatch(int fx, const float* const* ein, const float* const* hin, float* const* eout,
-                   float* const* hout, const float4* ce4, const float4* ch4, const Box3& BE, const Box3& BH,
-                   float cb, float db, int nx, int ny, int nz, const Box3* b, const Box3& O, int xchunk, int steps,
-                   const int* src, const TbSrc& sv, const TfDev* tf, const float* gtab, const AmpDev& amp,
-                   hipStream_t s, const DrDev& dr = DrDev{}) {
+int tb_mr_dispatch(int fx, const FdtdTbOpts& o, const float* const* ein, const float* const* hin,
+                   float* const* eout, float* const* hout, const float4* ce4, const float4* ch4, const Box3& BE,
+                   const Box3& BH, float cb, float db, int nx, int ny, int nz, const Box3* b, const Box3& O,
+                   int xchunk, int steps, const int* src, const TbSrc& sv, const TfDev* tf, const float* gtab,
+                   const AmpDev& amp, hipStream_t s, const DrDev& dr = DrDev{}) {
   if (xchunk <= 0 && (fx & 4)) {
     // tuning: x chunk of the TF/SF variant's passes (FDTD3D_TF_XCHUNK, 0 automatic)
     static const int tfx = [] {
@@ -420,8 +404,9 @@ int tb_mr_dispatch(int fx, const float* const* ein, const float* const* hin, flo
     }();
     if (tfx > 0) xchunk = tfx;
   }
-  if (xchunk <= 0) xchunk = tb_mr_xchunk(fx, O, steps);
-#define MR_ARGS fx, ein, hin, eout, hout, ce4, ch4, BE, BH, cb, db, nx, ny, nz, b, O, xchunk, src, sv, tf, gtab, amp, s, dr
+  if (xchunk <= 0) xchunk = tb_mr_xchunk(fx, o, O, steps);
+#define MR_ARGS \
+  fx, o, ein, hin, eout, hout, ce4, ch4, BE, BH, cb, db, nx, ny, nz, b, O, xchunk, src, sv, tf, gtab, amp, s, dr
   switch (steps) {
     case 1: return launch_tb_mr_sel<1>(MR_ARGS);
     case 2: return launch_tb_mr_sel<2>(MR_ARGS);
@@ -483,31 +468,8 @@ __global__ __launch_bounds__(1024) void k_tfsf_pass(R* __restrict__ einc, R* __r
 
 }  // namespace
 
-// lane width of the blocked kernel (tuning / tests): 0 = automatic, 2, 4
-FDTD_API void fdtd_set_tb_vec(int v) { g_tb_vec = (v == 2 || v == 4) ? v : 0; }
-// rows per wave of the blocked kernel: 0 = automatic, 1, 2 (2 rows of 32 lanes:
-// a 32-row tile, halving the y-halo re-reads of float2 lanes)
-FDTD_API void fdtd_set_tb_rows(int r) { g_tb_rows = (r == 1 || r == 2) ? r : 0; }
-// XCD-aware tile order of the blocked kernel (1 = on, default)
-FDTD_API void fdtd_set_tb_xcd(int on) { g_tb_xcd = on ? 1 : 0; }
-// adjacent y rows carried per wave (k_tb3d_mr): 0 = automatic, 1 = the
-// single-row kernel, 2
-FDTD_API void fdtd_set_tb_mrows(int r) { g_tb_mrows = (r == 1 || r == 2) ? r : 0; }
-// multi-row kernel variant (tuning): bit 0 deferred stores, bit 1 two planes
-// prefetched, bit 2 XCD-contiguous tile order
-FDTD_API void fdtd_set_tb_variant(int v) {
-  g_tb_variant = v & 3;
-  g_tb_mr_xcd = (v >> 2) & 1;      // bit 2: XCD-contiguous tile order
-  g_tb_mr_noallin = (v >> 3) & 1;  // bit 3: no interior fast path (A/B)
-}
-// patch order of the multi-row kernel's XCD tile run: pz x py tiles (0: z fastest)
-FDTD_API void fdtd_set_tb_patch(int pz, int py) {
-  g_tb_patch = (pz > 0 && py > 0 && pz < 256 && py < 256) ? ((pz << 8) | (py << 16)) : 0;
-}
-// Drude variant tile shape (tuning): 0 = 8 waves x 2 rows, 1 = 16 waves x 1 row
-FDTD_API void fdtd_set_tb_dr_shape(int v) { g_tb_dr_shape = v == 1 ? 1 : 0; }
-// plain multi-row tile shape (tuning): 0 = 16 waves x 2 rows, 1 = 8 waves x 4 rows
-FDTD_API void fdtd_set_tb_mr_shape(int v) { g_tb_mr_shape = (v == 1 || v == 2) ? v : 0; }
+// sizeof(FdtdTbOpts) as this library was built (ABI check of the callers that fill one)
+FDTD_API int fdtd_tb_opts_size() { return (int)sizeof(FdtdTbOpts); }
 // largest steps-per-pass the blocked kernels accept
 FDTD_API int fdtd_tb_max_steps() { return 6; }
 
@@ -515,17 +477,19 @@ FDTD_API int fdtd_tb_max_steps() { return 6; }
 // on the output box `obox` (lo[3], hi[3]).  `boxes` = 6 update boxes
 // (Ex Ey Ez Hx Hy Hz).  `src` = {i, j, k, comp} of a hard E point source (comp
 // -1: none) with the value of each of the T E half steps in `src_vals`.
+// `opts` = the tile options of this pass (capi.h FdtdTbOpts; null: defaults).
 FDTD_API int fdtd_tb3d_v4_f32(const float* const* ein, const float* const* hin, float* const* eout,
                               float* const* hout, const float* const* cbs, const float* const* dbs, double cb,
                               double db, int nx, int ny, int nz, const int* boxes, const int* obox, int xchunk,
-                              int steps, const int* src, const double* src_vals, void* stream) {
+                              int steps, const int* src, const double* src_vals, const FdtdTbOpts* opts,
+                              void* stream) {
   if (nz % 4 != 0 || steps < 1 || steps > 6) return (int)hipErrorInvalidValue;
-  Box3 b[6];
-  for (int n = 0; n < 6; ++n) b[n] = make_box(boxes + 6 * n);
-  const Box3 O = make_box(obox);
-  if (box_empty(O)) return 0;
-  TbSrc sv;
-  for (int l = 0; l < 8; ++l) sv.v[l] = (src[3] >= 0 && l < steps) ? (float)src_vals[l] : 0.f;
+  TbPass<TbSrc> p;
+  if (!tb_pass(p, boxes, obox, steps, src, src_vals)) return 0;
+  const Box3* b = p.b;
+  const Box3& O = p.O;
+  const TbSrc& sv = p.sv;
+  const FdtdTbOpts o = tb_opts(opts);
   hipStream_t s = (hipStream_t)stream;
   // per-cell coefficients of either kind (a null kind uses its scalar)
   const bool pc = cbs[0] != nullptr || dbs[0] != nullptr;
@@ -533,24 +497,22 @@ FDTD_API int fdtd_tb3d_v4_f32(const float* const* ein, const float* const* hin, 
   // multi-row kernel for uniform media: automatic from 4 steps on, required
   // above 4 (full per-cell planes run on the single-row kernel; the sparse
   // per-cell form is fdtd_tb3d_sparse_f32)
-  const int MR = g_tb_mrows ? g_tb_mrows : (steps >= 4 && !pc ? MR_AUTO_ROWS : 1);
+  const int MR = o.mrows ? o.mrows : (steps >= 4 && !pc ? MR_AUTO_ROWS : 1);
   if (!pc && (MR > 1 || steps > 4)) {
     const Box3 nb = make_box(kNoBox);
-    return tb_mr_dispatch(0, ein, hin, eout, hout, nullptr, nullptr, nb, nb, fcb, fdb, nx, ny, nz, b, O, xchunk,
+    return tb_mr_dispatch(0, o, ein, hin, eout, hout, nullptr, nullptr, nb, nb, fcb, fdb, nx, ny, nz, b, O, xchunk,
                           steps, src, sv, nullptr, nullptr, AmpDev{}, s);
   }
   if (steps > 4) return (int)hipErrorInvalidValue;
+  const int V = o.vec ? o.vec : (steps <= 2 ? 4 : 2);
+  const int R = o.rows ? o.rows : 1;  // 2 rows per wave measured slower (228k vs 245k, T=4)
   if (xchunk <= 0) {
-    const int V = g_tb_vec ? g_tb_vec : (steps <= 2 ? 4 : 2);
-    const int R = g_tb_rows ? g_tb_rows : 1;
     const int HL = (steps + V - 1) / V;
     const long long gz = cdiv(O.hi[2] - (O.lo[2] & ~(V - 1)), (64 / R - 2 * HL) * V);
     const long long gy = cdiv(O.hi[1] - O.lo[1], TBW * R - 2 * steps);
     xchunk = pick_xchunk(gz * gy, O.hi[0] - O.lo[0], steps);
   }
-  const int V = g_tb_vec ? g_tb_vec : (steps <= 2 ? 4 : 2);
-  const int R = g_tb_rows ? g_tb_rows : 1;  // 2 rows per wave measured slower (228k vs 245k, T=4)
-#define TB_ARGS pc, ein, hin, eout, hout, cbs, dbs, fcb, fdb, nx, ny, nz, b, O, xchunk, src, sv, s
+#define TB_ARGS pc, ein, hin, eout, hout, cbs, dbs, fcb, fdb, nx, ny, nz, b, O, xchunk, src, sv, s, o.xcd
 #define TB_CASE(TT)                                                                     \
   case TT:                                                                              \
     if (V == 4) return R == 2 ? launch_tb_pc<TT, 4, 2>(TB_ARGS) : launch_tb_pc<TT, 4, 1>(TB_ARGS); \
@@ -609,20 +571,16 @@ FDTD_API int fdtd_tb3d_ext_f32(const float* const* ein, const float* const* hin,
                                float* const* hout, const void* ce4, const int* ebox, const void* ch4,
                                const int* hbox, double cb, double db, int nx, int ny, int nz, const int* boxes,
                                const int* obox, int xchunk, int steps, const int* src, const double* src_vals,
-                               const void* tf, const float* gtab, void* stream) {
+                               const void* tf, const float* gtab, const FdtdTbOpts* opts, void* stream) {
   if (nz % 4 != 0 || steps < 1 || steps > 6) return (int)hipErrorInvalidValue;
-  Box3 b[6];
-  for (int n = 0; n < 6; ++n) b[n] = make_box(boxes + 6 * n);
-  const Box3 O = make_box(obox);
-  if (box_empty(O)) return 0;
+  TbPass<TbSrc> p;
+  if (!tb_pass(p, boxes, obox, steps, src, src_vals)) return 0;
   const Box3 BE = make_box(ce4 ? ebox : kNoBox), BH = make_box(ch4 ? hbox : kNoBox);
-  TbSrc sv;
-  for (int l = 0; l < 8; ++l) sv.v[l] = (src[3] >= 0 && l < steps) ? (float)src_vals[l] : 0.f;
   const int fx = (ce4 && !box_empty(BE) ? 1 : 0) | (ch4 && !box_empty(BH) ? 2 : 0) | (tf && gtab ? 4 : 0);
   if (tf && gtab) tf = tfsf_experiment(tf, (hipStream_t)stream);
-  return tb_mr_dispatch(fx, ein, hin, eout, hout, (const float4*)(box_empty(BE) ? nullptr : ce4),
-                        (const float4*)(box_empty(BH) ? nullptr : ch4), BE, BH, (float)cb, (float)db, nx, ny, nz, b,
-                        O, xchunk, steps, src, sv, (const TfDev*)tf, gtab, AmpDev{}, (hipStream_t)stream);
+  return tb_mr_dispatch(fx, tb_opts(opts), ein, hin, eout, hout, (const float4*)(box_empty(BE) ? nullptr : ce4),
+                        (const float4*)(box_empty(BH) ? nullptr : ch4), BE, BH, (float)cb, (float)db, nx, ny, nz, p.b,
+                        p.O, xchunk, steps, src, p.sv, (const TfDev*)tf, gtab, AmpDev{}, (hipStream_t)stream);
 }
 
 // T <= 3 fused leapfrog steps with the amplitude (steady-state) update of
@@ -638,14 +596,10 @@ FDTD_API int fdtd_tb3d_amp_f32(const float* const* ein, const float* const* hin,
                                float* const* hout, double cb, double db, int nx, int ny, int nz, const int* boxes,
                                const int* obox, int xchunk, int steps, const int* src, const double* src_vals,
                                float* const* amp, const int* aboxes, double accuracy, unsigned* counts,
-                               void* stream) {
+                               const FdtdTbOpts* opts, void* stream) {
   if (nz % 4 != 0 || steps < 1 || steps > 3 || !counts) return (int)hipErrorInvalidValue;
-  Box3 b[6];
-  for (int n = 0; n < 6; ++n) b[n] = make_box(boxes + 6 * n);
-  const Box3 O = make_box(obox);
-  if (box_empty(O)) return 0;
-  TbSrc sv;
-  for (int l = 0; l < 8; ++l) sv.v[l] = (src[3] >= 0 && l < steps) ? (float)src_vals[l] : 0.f;
+  TbPass<TbSrc> p;
+  if (!tb_pass(p, boxes, obox, steps, src, src_vals)) return 0;
   // the six arrays are the component planes of one [x][6][y][z] buffer
   const long long plane = (long long)ny * nz;
   // (the component offset rides in the instruction's SGPR offset: keep it
@@ -663,8 +617,8 @@ FDTD_API int fdtd_tb3d_amp_f32(const float* const* ein, const float* const* hin,
   A.acc = (float)accuracy;
   A.k1 = src[4];
   const Box3 nb = make_box(kNoBox);
-  return tb_mr_dispatch(8, ein, hin, eout, hout, nullptr, nullptr, nb, nb, (float)cb, (float)db, nx, ny, nz, b, O,
-                        xchunk, steps, src, sv, nullptr, nullptr, A, (hipStream_t)stream);
+  return tb_mr_dispatch(8, tb_opts(opts), ein, hin, eout, hout, nullptr, nullptr, nb, nb, (float)cb, (float)db, nx,
+                        ny, nz, p.b, p.O, xchunk, steps, src, p.sv, nullptr, nullptr, A, (hipStream_t)stream);
 }
 
 // T <= 5 fused leapfrog steps over the output box with the Drude box B
@@ -678,13 +632,12 @@ FDTD_API int fdtd_tb3d_drude_f32(const float* const* ein, const float* const* hi
                                  float* const* hout, double cb, double db, int nx, int ny, int nz, const int* boxes,
                                  const int* obox, int xchunk, int steps, const int* src, const double* src_vals,
                                  const int* bbox, void* const* sin, void* const* sout, const void* lut, int nid,
-                                 double cbd, void* stream) {
+                                 double cbd, const FdtdTbOpts* opts, void* stream) {
   if (nz % 4 != 0 || steps < 1 || steps > 5 || !sin || !sout || !lut || nid < 1 || nid > DR_MAX_IDS)
     return (int)hipErrorInvalidValue;
-  Box3 b[6];
-  for (int n = 0; n < 6; ++n) b[n] = make_box(boxes + 6 * n);
-  const Box3 O = make_box(obox);
-  if (box_empty(O)) return 0;
+  TbPass<TbSrc> p;
+  if (!tb_pass(p, boxes, obox, steps, src, src_vals)) return 0;
+  const Box3* b = p.b;
   DrDev D;
   D.B = make_box(bbox);
   if (box_empty(D.B)) return (int)hipErrorInvalidValue;
@@ -704,11 +657,9 @@ FDTD_API int fdtd_tb3d_drude_f32(const float* const* ein, const float* const* hi
   D.lut = (const float4*)lut;
   D.nid = nid;
   D.cbd = (float)cbd;
-  TbSrc sv;
-  for (int l = 0; l < 8; ++l) sv.v[l] = (src[3] >= 0 && l < steps) ? (float)src_vals[l] : 0.f;
   const Box3 nb = make_box(kNoBox);
-  return tb_mr_dispatch(16, ein, hin, eout, hout, nullptr, nullptr, nb, nb, (float)cb, (float)db, nx, ny, nz, b, O,
-                        xchunk, steps, src, sv, nullptr, nullptr, AmpDev{}, (hipStream_t)stream, D);
+  return tb_mr_dispatch(16, tb_opts(opts), ein, hin, eout, hout, nullptr, nullptr, nb, nb, (float)cb, (float)db, nx,
+                        ny, nz, b, p.O, xchunk, steps, src, p.sv, nullptr, nullptr, AmpDev{}, (hipStream_t)stream, D);
 }
 
 // size of the TfDev block the host fills (ABI check)

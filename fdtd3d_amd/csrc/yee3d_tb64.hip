@@ -5,8 +5,8 @@
 // neighbours by DPP wave shifts), with scalar fp64 lanes: every carried
 // value takes two VGPRs, so one cell per lane (two cells spill from T = 2
 // on).  Default tiles are 32 x 32 (each wave holds two y rows of 32 z lanes,
-// HALF below); the 16-row x 64-lane shape stays selectable
-// (fdtd_set_tb64_shape).  T halo rows / lanes on each side, 1..5 steps.
+// HALF below); the 16-row x 64-lane shape stays selectable per pass
+// (FdtdTbOpts.half64 = 0, capi.h).  T halo rows / lanes on each side, 1..5 steps.
 // 1024^3 vacuum, one MI355X (bench.py --dtype f64): 16 x 64 tiles T = 4
 // 105-109k Mcells/s; 32 x 32 tiles T = 4 114k; + stores deferred one plane
 // (no store-ack drain per plane) 120k; T = 5 116k.
@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "capi.h"
 #include "common.h"
 #include "tfsf_dev.h"
 
@@ -97,7 +98,6 @@ struct DrS64 {
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
 int g_num_cus64 = 0;
-bool g_tb64_half = true;
 
 // x chunk minimising rounds x (chunk + 2T) (same model as yee3d_tb.hip)
 int pick_xchunk64(long long tiles_yz, int nxo, int T) {
@@ -508,17 +508,16 @@ __global__ __launch_bounds__(64 * NW) void k_tb3d_f64(
 // patch order of the XCD tile run: pz | (py << 8), 0 = z fastest.  Default
 // 2 x 8 (z x y tiles): 1024^3 fp64 123.3k vs 118.3k Mcells/s z fastest, means
 // of 3 / 4 alternating runs (profiles/fp64_patch_r5.md); FDTD3D_TB64_PATCH=
-// "PZxPY" at first use ("0x0": z fastest), fdtd_set_tb64_patch
-int g_tb64_patch = -1;
+// "PZxPY" at first use ("0x0": z fastest)
 int tb64_patch() {
-  if (g_tb64_patch < 0) {
-    g_tb64_patch = 2 | (8 << 8);
+  static const int patch = [] {
     const char* e = getenv("FDTD3D_TB64_PATCH");
     int pz = 0, py = 0;
     if (e && sscanf(e, "%dx%d", &pz, &py) == 2 && pz >= 0 && py >= 0 && pz < 256 && py < 256)
-      g_tb64_patch = (pz > 0 && py > 0) ? (pz | (py << 8)) : 0;
-  }
-  return g_tb64_patch;
+      return (pz > 0 && py > 0) ? (pz | (py << 8)) : 0;
+    return 2 | (8 << 8);
+  }();
+  return patch;
 }
 
 template <int T, int R, bool HALF, int NW = TBW>
@@ -561,33 +560,23 @@ int launch_tb64(bool pc, const double* const* ein, const double* const* hin, dou
 
 FDTD_API int fdtd_tb64_max_steps() { return 5; }
 
-// 1: two rows of 32 lanes per wave (32 x 32 tiles, default); 0: one row of
-// 64 lanes (16 x 64 tiles)
-FDTD_API void fdtd_set_tb64_shape(int half) { g_tb64_half = half != 0; }
-
-// patch order of the fp64 kernel's XCD tile run: pz x py tiles (0: z fastest)
-FDTD_API void fdtd_set_tb64_patch(int pz, int py) {
-  g_tb64_patch = (pz > 0 && py > 0 && pz < 256 && py < 256) ? (pz | (py << 8)) : 0;
-}
-
 namespace {
+// ``opts``: half64 != 0 (and null) = two rows of 32 lanes per wave (32 x 32
+// tiles), 0 = one row of 64 lanes (16 x 64 tiles)
 int tb64_run(const double* const* ein, const double* const* hin, double* const* eout, double* const* hout,
              const double* const* cbs, const double* const* dbs, double cb, double db, int nx, int ny, int nz,
              const int* boxes, const int* obox, int xchunk, int steps, const int* src, const double* src_vals,
-             const tb3d::TfDev* tf, const double* gtab, void* stream) {
+             const tb3d::TfDev* tf, const double* gtab, const FdtdTbOpts* opts, void* stream) {
   if (steps < 1 || steps > 5) return (int)hipErrorInvalidValue;
-  Box3 b[6];
-  for (int n = 0; n < 6; ++n) b[n] = make_box(boxes + 6 * n);
-  const Box3 O = make_box(obox);
-  if (box_empty(O)) return 0;
-  TbSrc64 sv;
-  for (int l = 0; l < 8; ++l) sv.v[l] = (src[3] >= 0 && l < steps) ? src_vals[l] : 0.0;
+  TbPass<TbSrc64> p;
+  if (!tb_pass(p, boxes, obox, steps, src, src_vals)) return 0;
   const bool pc = cbs[0] != nullptr || dbs[0] != nullptr;  // a null kind uses its scalar
   hipStream_t s = (hipStream_t)stream;
   // one row per wave: two rows of fp64 state spill from T = 2 on
 #define TB64(TT, HF) \
-  launch_tb64<TT, 1, HF>(pc, ein, hin, eout, hout, cbs, dbs, cb, db, nx, ny, nz, b, O, xchunk, src, sv, s, tf, gtab)
-  if (g_tb64_half) {
+  launch_tb64<TT, 1, HF>(pc, ein, hin, eout, hout, cbs, dbs, cb, db, nx, ny, nz, p.b, p.O, xchunk, src, p.sv, s, tf, \
+                         gtab)
+  if (!opts || opts->half64) {
     switch (steps) {
       case 1: return TB64(1, true);
       case 2: return TB64(2, true);
@@ -614,9 +603,9 @@ int tb64_run(const double* const* ein, const double* const* hin, double* const* 
 FDTD_API int fdtd_tb3d_f64(const double* const* ein, const double* const* hin, double* const* eout,
                            double* const* hout, const double* const* cbs, const double* const* dbs, double cb,
                            double db, int nx, int ny, int nz, const int* boxes, const int* obox, int xchunk,
-                           int steps, const int* src, const double* src_vals, void* stream) {
+                           int steps, const int* src, const double* src_vals, const FdtdTbOpts* opts, void* stream) {
   return tb64_run(ein, hin, eout, hout, cbs, dbs, cb, db, nx, ny, nz, boxes, obox, xchunk, steps, src, src_vals,
-                  nullptr, nullptr, stream);
+                  nullptr, nullptr, opts, stream);
 }
 
 // ... with the Drude box folded in (DrDev64; the fp64 counterpart of
@@ -624,17 +613,17 @@ FDTD_API int fdtd_tb3d_f64(const double* const* ein, const double* const* hin, d
 // boxes), ``sin`` / ``sout`` = the two 32-byte state records per cell of B in
 // / out (distinct), ``lut`` = [3][nid][4] doubles (b0 cbd, b2, m1, m2),
 // ``cbd`` the D coefficient; uniform media elsewhere.  Tiles of 8 waves x two
-// 32-lane rows (the state of T - 1 levels rides in registers: <= 256 VGPRs).
+// 32-lane rows (the state of T - 1 levels rides in registers: <= 256 VGPRs):
+// the one shape of this variant, ``opts`` selects nothing here.
 FDTD_API int fdtd_tb3d_drude_f64(const double* const* ein, const double* const* hin, double* const* eout,
                                  double* const* hout, double cb, double db, int nx, int ny, int nz, const int* boxes,
                                  const int* obox, int xchunk, int steps, const int* src, const double* src_vals,
                                  const int* bbox, void* const* sin, void* const* sout, const double* lut, int nid,
-                                 double cbd, void* stream) {
+                                 double cbd, const FdtdTbOpts* opts, void* stream) {
   if (steps < 1 || steps > 5 || !sin || !sout || !lut || nid < 1 || nid > DR64_MAX_IDS) return (int)hipErrorInvalidValue;
-  Box3 b[6];
-  for (int n = 0; n < 6; ++n) b[n] = make_box(boxes + 6 * n);
-  const Box3 O = make_box(obox);
-  if (box_empty(O)) return 0;
+  TbPass<TbSrc64> p;
+  if (!tb_pass(p, boxes, obox, steps, src, src_vals)) return 0;
+  const Box3* b = p.b;
   DrDev64 D;
   D.B = make_box(bbox);
   if (box_empty(D.B)) return (int)hipErrorInvalidValue;
@@ -654,13 +643,11 @@ FDTD_API int fdtd_tb3d_drude_f64(const double* const* ein, const double* const* 
   D.lut = lut;
   D.nid = nid;
   D.cbd = cbd;
-  TbSrc64 sv;
-  for (int l = 0; l < 8; ++l) sv.v[l] = (src[3] >= 0 && l < steps) ? src_vals[l] : 0.0;
   const double* none[3] = {nullptr, nullptr, nullptr};
   hipStream_t s = (hipStream_t)stream;
 #define TB64D(TT) \
-  launch_tb64<TT, 1, true, 8>(false, ein, hin, eout, hout, none, none, cb, db, nx, ny, nz, b, O, xchunk, src, sv, s, \
-                              nullptr, nullptr, &D)
+  launch_tb64<TT, 1, true, 8>(false, ein, hin, eout, hout, none, none, cb, db, nx, ny, nz, b, p.O, xchunk, src, p.sv, \
+                              s, nullptr, nullptr, &D)
   switch (steps) {
     case 1: return TB64D(1);
     case 2: return TB64D(2);
@@ -679,8 +666,8 @@ FDTD_API int fdtd_tb3d_tf_f64(const double* const* ein, const double* const* hin
                               double* const* hout, const double* const* cbs, const double* const* dbs, double cb,
                               double db, int nx, int ny, int nz, const int* boxes, const int* obox, int xchunk,
                               int steps, const int* src, const double* src_vals, const void* tf, const double* gtab,
-                              void* stream) {
+                              const FdtdTbOpts* opts, void* stream) {
   if (!tf || !gtab) return (int)hipErrorInvalidValue;
   return tb64_run(ein, hin, eout, hout, cbs, dbs, cb, db, nx, ny, nz, boxes, obox, xchunk, steps, src, src_vals,
-                  (const tb3d::TfDev*)tf, gtab, stream);
+                  (const tb3d::TfDev*)tf, gtab, opts, stream);
 }

@@ -40,7 +40,7 @@ class HipMonitorOps:
     ``_check_tensor`` of :class:`~.hip_ops.HipOps`."""
 
     def _check_ent_size(self, name: str, fn: str, size: int) -> None:
-        if int(getattr(self.lib, "fdtd_%s_ent_size" % fn)()) != size:
+        if int(getattr(self.lib.raw, "fdtd_%s_ent_size" % fn)()) != size:
             raise HipError("%sEnt layout mismatch" % name)
 
     def _check_operand(self, op_name: str, operand, extent, k: int, too_large: str = "accumulator block too large"):
@@ -62,7 +62,7 @@ class HipMonitorOps:
         if not 1 <= entries.k <= DFT_MAX_K:
             raise HipError("dft_accumulate: 1..%d frequencies, got %d" % (DFT_MAX_K, entries.k))
         self._check_ent_size("Dft", "dft", DFT_ENT_SIZE)
-        if int(self.lib.fdtd_dft_max_k()) != DFT_MAX_K:
+        if int(self.lib.raw.fdtd_dft_max_k()) != DFT_MAX_K:
             raise HipError("DftEnt layout mismatch")
         v = vec_width(self.dtype)
         rows = []

@@ -89,36 +89,48 @@ def _empty(b: Box) -> bool:
     return any(b[1][d] <= b[0][d] for d in range(3))
 
 
-class _RecFn:
-    """A ``libfdtd3d_hip`` entry point that, while its ops object records
-    (:meth:`HipOps.record`), also appends (function, arguments, returns a
-    status) to the record: every argument is already a ctypes value, so the
-    call replays as is."""
-    __slots__ = ("f", "ops", "status")
+class TbOpts(ctypes.Structure):
+    """Tile options of one blocked 3D pass (csrc/capi.h ``FdtdTbOpts``)."""
+    _fields_ = [(n, c_int) for n in ("vec", "rows", "xcd", "mrows", "variant", "mr_shape", "dr_shape", "half64")]
 
-    def __init__(self, f, ops, status):
-        self.f, self.ops, self.status = f, ops, status
+
+class _RecFn:
+    """A launch of ``libfdtd3d_hip`` that, while its ops object records
+    (:meth:`HipOps.record`), also appends (function, arguments) to the
+    record: every argument is already a ctypes value, so the call replays as
+    is."""
+    __slots__ = ("f", "ops")
+
+    def __init__(self, f, ops):
+        self.f, self.ops = f, ops
 
     def __call__(self, *args):
         rec = self.ops._rec
         if rec is not None:
-            rec.append((self.f, args, self.status))
+            rec.append((self.f, args))
         return self.f(*args)
 
 
+# the library's process-wide knobs (chain, fused and 2D kernels): void, not launches
+_SETTERS = ("fdtd_set_chain_v4", "fdtd_set_chain_split", "fdtd_set_fused_rows", "fdtd_set_lowdim_wgs")
+
+
 class _LibProxy:
-    """``libfdtd3d_hip`` seen through :class:`_RecFn` wrappers."""
+    """The launches of ``libfdtd3d_hip`` as :class:`_RecFn` wrappers: every
+    entry point fetched here launches kernels and returns an hipError status,
+    so it is recorded and its status checked on replay.  What launches
+    nothing stays out of a record: the knob setters ``_SETTERS`` come back as
+    the plain functions, and the size and limit queries are asked of ``raw``,
+    the library itself."""
 
     def __init__(self, lib, ops):
-        self._lib, self._ops, self._w = lib, ops, {}
+        self.raw, self._ops, self._w = lib, ops, {}
 
     def __getattr__(self, name):
         w = self._w.get(name)
         if w is None:
-            f = getattr(self._lib, name)
-            # the knob setters (fdtd_set_tb_*, ...) return void; everything else an hipError status
-            status = not (name.startswith("fdtd_set_") and not name.startswith("fdtd_set_value"))
-            w = self._w[name] = _RecFn(f, self._ops, status) if name.startswith("fdtd_") else f
+            f = getattr(self.raw, name)
+            w = self._w[name] = f if name in _SETTERS else _RecFn(f, self._ops)
         return w
 
 
@@ -143,6 +155,10 @@ class HipOps(HipMonitorOps):
         self.suf = {torch.float32: "f32", torch.float64: "f64"}[dtype]
         self._rec = None
         self.lib = _LibProxy(load_library(), self)
+        if int(self.lib.raw.fdtd_tb_opts_size()) != ctypes.sizeof(TbOpts):
+            raise HipError("FdtdTbOpts layout mismatch (%d vs %d bytes)" % (self.lib.raw.fdtd_tb_opts_size(),
+                                                                            ctypes.sizeof(TbOpts)))
+        self._tfdev_size = int(self.lib.raw.fdtd_tfdev_size())
         self.xchunk = xchunk
         self._fn: Dict[str, object] = {}
         self.launches = 0
@@ -157,10 +173,11 @@ class HipOps(HipMonitorOps):
 
     # ------------------------------------------------------------ launch records
     def record(self, rec: Optional[list]) -> None:
-        """Start (a list) / stop (None) recording every library call: the
-        calls still run; :meth:`replay` re-issues the recorded ones.  Only
-        kernel launches through this object are recorded -- the recorded
-        section must not depend on torch operations."""
+        """Start (a list) / stop (None) recording the launches of this
+        object: they still run; :meth:`replay` re-issues the recorded ones.
+        Only kernel launches are recorded (a blocked pass is one entry, its
+        tile options among the arguments) -- the recorded section must not
+        depend on torch operations."""
         self._rec = rec
 
     @staticmethod
@@ -168,9 +185,9 @@ class HipOps(HipMonitorOps):
         """Re-issue recorded library calls in order, as recorded (pointers,
         boxes and the stream are baked into the arguments): a pass's launches
         straight from a list, without the Python planning around them."""
-        for f, args, status in rec:
+        for f, args in rec:
             rc = f(*args)
-            if status and rc:
+            if rc:
                 raise HipError("replayed launch failed: hipError %d" % rc)
 
     # ------------------------------------------------------------ validation
@@ -333,7 +350,7 @@ class HipOps(HipMonitorOps):
         self.launches += 1
 
     def resident_1d_max_cells(self) -> int:
-        return int(self.lib.fdtd_res1d_max_cells(c_int(self.dtype.itemsize)))
+        return int(self.lib.raw.fdtd_res1d_max_cells(c_int(self.dtype.itemsize)))
 
     def resident_1d(self, F: Dict[str, torch.Tensor], boxes: Dict[str, Box], cb: Dict[str, Coef], nsteps: int,
                     src_i: Optional[int] = None, vals: Optional[torch.Tensor] = None) -> None:
@@ -660,7 +677,7 @@ class HipOps(HipMonitorOps):
         self.launches += 1
 
     def box_ent_size(self) -> int:
-        return int(self.lib.fdtd_box_ent_size())
+        return int(self.lib.raw.fdtd_box_ent_size())
 
     def unpack(self, tensors: Sequence[torch.Tensor], box: Box, buf: torch.Tensor) -> None:
         shape = tuple(tensors[0].shape)
@@ -878,9 +895,7 @@ class HipOps(HipMonitorOps):
         if not (1 <= T <= 8):
             raise HipError("tfsf_pass: 1..8 steps")
         sfx = "f32" if self.dtype == torch.float32 else "f64"
-        if int(self.lib.fdtd_tfdev_size()) != 4 * sets.dev.numel():
-            raise HipError("TfDev layout mismatch (%d vs %d bytes)" % (self.lib.fdtd_tfdev_size(),
-                                                                       4 * sets.dev.numel()))
+        self._check_tfdev(sets)
         need = T * max(1, sets.ld)
         tabs = sets.__dict__.setdefault("gtab", {})
         g = tabs.get(slot)
@@ -911,6 +926,87 @@ class HipOps(HipMonitorOps):
         self.launches += 1
         return g
 
+    def _check_tfdev(self, sets) -> None:
+        """The host's set table has the library's TfDev layout (its size is
+        asked once per ops object)."""
+        if self._tfdev_size != 4 * sets.dev.numel():
+            raise HipError("TfDev layout mismatch (%d vs %d bytes)" % (self._tfdev_size, 4 * sets.dev.numel()))
+
+    def _tb_opts(self, steps: int = 0, thin_obox: Optional[Box] = None):
+        """The tile options of one blocked 3D pass (``FdtdTbOpts``) from this
+        object's ``tb_*`` attributes: every blocked launch passes them.
+        ``thin_obox`` (the plain fp32 path gives its output box): thin y
+        shells of a decomposed pass take 16-row tiles, which waste half as
+        many rows as the 32-row multi-row tiles -- the single-row kernel's,
+        or the multi-row kernel's 8-wave form (tb_thin_mr16)."""
+        mr, mr_shape = self.tb_mrows, self.tb_mr_shape
+        if (thin_obox is not None and mr == 0 and self.tb_thin_single_row and steps <= 4
+                and thin_obox[1][1] - thin_obox[0][1] <= 8):
+            if self.tb_thin_mr16:
+                mr_shape = 2
+            else:
+                mr = 1
+        return ctypes.byref(TbOpts(self.tb_vec, self.tb_rows, self.tb_xcd, mr, self.tb_variant, mr_shape,
+                                   self.tb_dr_shape, self.tb64_half))
+
+    @staticmethod
+    def _check_inside(op: str, boxes: Sequence[Box], shape, nd: int = 3, empty_too: bool = False) -> None:
+        for b in boxes:
+            if (empty_too or not _empty(b)) and any(b[0][d] < 0 or b[1][d] > shape[d] for d in range(nd)):
+                raise HipError("%s: box %s outside array %s" % (op, b, shape))
+
+    @staticmethod
+    def _tb_source(op: str, sources, comps, shape, nd: int = 3):
+        """The hard point source of a blocked pass -- ``sources`` = per step
+        (component, local index, value) or None, the same point at every
+        step -- as the kernels take it: ``src`` = nd indices + the
+        component's place in ``comps`` (-1: no source), ``vals`` = 8 values."""
+        src, vals = [-1] * (nd + 1), [0.0] * 8
+        if sources is not None and any(s is not None for s in sources):
+            first = next(s for s in sources if s is not None)
+            comp, idx = first[0], tuple(first[1])
+            if comp not in comps:
+                raise HipError("%s: point source on %s only, got %s" % (op, "/".join(comps), comp))
+            if not all(0 <= idx[d] < shape[d] for d in range(nd)):
+                raise HipError("%s: source index %s outside array %s" % (op, idx, shape))
+            for l, s in enumerate(sources):
+                if s is None or s[0] != comp or tuple(s[1]) != idx:
+                    raise HipError("%s: the source must be the same point at every step" % op)
+                vals[l] = float(s[2])
+            src = list(idx[:nd]) + [comps.index(comp)]
+        return (c_int * len(src))(*src), (c_double * 8)(*vals)
+
+    def _tb3d_pass(self, op: str, fin, fout, boxes: Dict[str, Box], obox: Box, cb: Dict[str, Coef],
+                   more_boxes: Sequence[Box] = (), uniform: str = ""):
+        """What the blocked 3D wrappers share.  Validates the twelve field
+        tensors (this backend's, one shape, ``fin`` / ``fout`` distinct; fp32:
+        nz % 4 == 0), that the non-empty ones of the update boxes, ``obox`` and
+        ``more_boxes`` lie inside the arrays, and the coefficients: per-cell
+        ones raise ``uniform`` (the op's message) when set, scalars must
+        agree per kind.  Returns (shape, per-cell?, (cb, db) scalars, the four
+        3-pointer arrays E in, H in, E out, H out, and the arguments nx, ny,
+        nz, boxes, obox, xchunk)."""
+        E, H = ("Ex", "Ey", "Ez"), ("Hx", "Hy", "Hz")
+        shape = tuple(fin["Ex"].shape)
+        if self.dtype == torch.float32 and shape[2] % 4 != 0:
+            raise HipError("fp32 %s needs nz %% 4 == 0, got %s" % (op, shape))
+        for c in E + H:
+            self._check_tensor(fin[c], shape)
+            self._check_tensor(fout[c], shape)
+            if fin[c].data_ptr() == fout[c].data_ptr():
+                raise HipError("%s needs distinct in/out buffers" % op)
+        self._check_inside(op, [boxes[c] for c in E + H] + [obox] + list(more_boxes), shape)
+        percell = any(self._cell_or_none(cb[c]) is not None for c in E + H)
+        if percell and uniform:
+            raise HipError("%s: %s" % (op, uniform))
+        cbv, dbv = cb["Ex"].scalar, cb["Hx"].scalar
+        if not percell and (any(cb[c].scalar != cbv for c in E) or any(cb[c].scalar != dbv for c in H)):
+            raise HipError("%s: scalar coefficients must agree per kind" % op)
+        arr = lambda names, f: (c_vp * 3)(*[f[c].data_ptr() for c in names])
+        geom = (c_int(shape[0]), c_int(shape[1]), c_int(shape[2]), _box_arr([boxes[c] for c in E + H]),
+                _box_arr([obox]), c_int(self.tb_xchunk))
+        return shape, percell, (cbv, dbv), (arr(E, fin), arr(H, fin), arr(E, fout), arr(H, fout)), geom
+
     tb_amp_max_steps = 3  # amplitude passes: the kernel's LDS hand-off holds T - 1 levels
 
     def tb_amp_step(self, fin: Dict[str, torch.Tensor], fout: Dict[str, torch.Tensor], boxes: Dict[str, Box],
@@ -923,26 +1019,11 @@ class HipOps(HipMonitorOps):
         ``counts[l]`` (int32, device) gets the changed cells of step l added.
         ``line`` = (E component, i, j, k0, k1) of the hard z-line source, or
         None; ``vals`` its value per step.  Uniform media only."""
-        E, H = ("Ex", "Ey", "Ez"), ("Hx", "Hy", "Hz")
+        E = ("Ex", "Ey", "Ez")
         if self.dtype != torch.float32 or not (1 <= steps <= self.tb_amp_max_steps):
             raise HipError("amplitude passes: fp32, 1..%d steps" % self.tb_amp_max_steps)
-        shape = tuple(fin["Ex"].shape)
-        if shape[2] % 4 != 0:
-            raise HipError("fp32 tb_amp_step needs nz %% 4 == 0, got %s" % (shape,))
-        for c in E + H:
-            self._check_tensor(fin[c], shape)
-            self._check_tensor(fout[c], shape)
-            if fin[c].data_ptr() == fout[c].data_ptr():
-                raise HipError("tb_amp_step needs distinct in/out buffers")
-            if self._cell_or_none(cb[c]) is not None:
-                raise HipError("tb_amp_step: uniform media only")
-        for bx in list(boxes.values()) + [obox] + list(aboxes):
-            for d in range(3):
-                if not _empty(bx) and (bx[0][d] < 0 or bx[1][d] > shape[d]):
-                    raise HipError("box %s outside array %s" % (bx, shape))
-        cbv, dbv = cb["Ex"].scalar, cb["Hx"].scalar
-        if any(cb[c].scalar != cbv for c in E) or any(cb[c].scalar != dbv for c in H):
-            raise HipError("tb_amp_step: scalar coefficients must agree per kind")
+        shape, _, (cbv, dbv), ptrs, geom = self._tb3d_pass("tb_amp_step", fin, fout, boxes, obox, cb, aboxes,
+                                                           uniform="uniform media only")
         xs = self._check_amp(amps, shape)
         plane = shape[1] * shape[2]
         es = amps[0].element_size()
@@ -961,16 +1042,10 @@ class HipOps(HipMonitorOps):
                 raise HipError("tb_amp_step: bad line source %s" % (line,))
             src = [i, j, k0, E.index(comp), k1]
             v8[:steps] = [float(v) for v in vals[:steps]]
-        arr = lambda names, f: (c_vp * 3)(*[f[c].data_ptr() for c in names])
-        # the launcher picks the tile shape from the library's global: push this backend's knob
-        # (as tb_drude_step does), or the pass runs whatever shape the last plain tb_step left
-        self.lib.fdtd_set_tb_mr_shape(c_int(self.tb_mr_shape))
         rc = self.lib.fdtd_tb3d_amp_f32(
-            arr(E, fin), arr(H, fin), arr(E, fout), arr(H, fout), c_double(cbv), c_double(dbv), c_int(shape[0]),
-            c_int(shape[1]), c_int(shape[2]), _box_arr([boxes[c] for c in E + H]), _box_arr([obox]),
-            c_int(self.tb_xchunk), c_int(steps), (c_int * 5)(*src), (c_double * 8)(*v8),
+            *ptrs, c_double(cbv), c_double(dbv), *geom, c_int(steps), (c_int * 5)(*src), (c_double * 8)(*v8),
             (c_vp * 6)(*[a.data_ptr() for a in amps]), _box_arr(list(aboxes)), c_double(accuracy),
-            c_vp(counts.data_ptr()), _stream())
+            c_vp(counts.data_ptr()), self._tb_opts(), _stream())
         _check(rc, "tb3d_amp")
         self.launches += 1
 
@@ -988,25 +1063,12 @@ class HipOps(HipMonitorOps):
         ``drude["sout"]``; ``drude["lut"]`` = (3, nid, 4) float32 tuples
         (b0 cbd, b2, m1, m2), ``drude["cbd"]`` the D coefficient.  Uniform
         media elsewhere; ``sources`` as :meth:`tb_step`."""
-        E, H = ("Ex", "Ey", "Ez"), ("Hx", "Hy", "Hz")
+        E = ("Ex", "Ey", "Ez")
         if not (1 <= steps <= self.tb_drude_max_steps):
             raise HipError("Drude passes: 1..%d steps" % self.tb_drude_max_steps)
-        shape = tuple(fin["Ex"].shape)
-        f32 = self.dtype == torch.float32
-        if f32 and shape[2] % 4 != 0:
-            raise HipError("fp32 tb_drude_step needs nz %% 4 == 0, got %s" % (shape,))
-        for c in E + H:
-            self._check_tensor(fin[c], shape)
-            self._check_tensor(fout[c], shape)
-            if fin[c].data_ptr() == fout[c].data_ptr():
-                raise HipError("tb_drude_step needs distinct in/out buffers")
-            if self._cell_or_none(cb[c]) is not None:
-                raise HipError("tb_drude_step: uniform media outside the Drude box only")
         B = drude["box"]
-        for bx in list(boxes.values()) + [obox, B]:
-            for d in range(3):
-                if not _empty(bx) and (bx[0][d] < 0 or bx[1][d] > shape[d]):
-                    raise HipError("box %s outside array %s" % (bx, shape))
+        shape, _, (cbv, dbv), ptrs, geom = self._tb3d_pass("tb_drude_step", fin, fout, boxes, obox, cb, [B],
+                                                           uniform="uniform media outside the Drude box only")
         for c in E:
             b = boxes[c]
             if any(B[0][d] < b[0][d] or B[1][d] > b[1][d] for d in range(3)):
@@ -1019,31 +1081,12 @@ class HipOps(HipMonitorOps):
         lut = drude["lut"]
         nid = int(lut.shape[1])
         self._check_tensor(lut, (3, nid, 4))
-        cbv, dbv = cb["Ex"].scalar, cb["Hx"].scalar
-        if any(cb[c].scalar != cbv for c in E) or any(cb[c].scalar != dbv for c in H):
-            raise HipError("tb_drude_step: scalar coefficients must agree per kind")
-        src = [-1, -1, -1, -1]
-        vals = [0.0] * 8
-        if sources is not None and any(s is not None for s in sources):
-            first = next(s for s in sources if s is not None)
-            comp, idx = first[0], tuple(first[1])
-            if comp not in E or not all(0 <= idx[d] < shape[d] for d in range(3)):
-                raise HipError("tb_drude_step: E point source inside the array only")
-            for l, s in enumerate(sources):
-                if s is None or s[0] != comp or tuple(s[1]) != idx:
-                    raise HipError("tb_drude_step: the source must be the same point at every step")
-                vals[l] = float(s[2])
-            src = [idx[0], idx[1], idx[2], E.index(comp)]
-        arr = lambda names, f: (c_vp * 3)(*[f[c].data_ptr() for c in names])
+        src, vals = self._tb_source("tb_drude_step", sources, E, shape)
         two = lambda ts: (c_vp * 2)(*[t.data_ptr() for t in ts])
-        if f32:
-            self.lib.fdtd_set_tb_dr_shape(c_int(self.tb_dr_shape))
+        f32 = self.dtype == torch.float32
         rc = (self.lib.fdtd_tb3d_drude_f32 if f32 else self.lib.fdtd_tb3d_drude_f64)(
-            arr(E, fin), arr(H, fin), arr(E, fout), arr(H, fout), c_double(cbv), c_double(dbv), c_int(shape[0]),
-            c_int(shape[1]), c_int(shape[2]), _box_arr([boxes[c] for c in E + H]), _box_arr([obox]),
-            c_int(self.tb_xchunk), c_int(steps), (c_int * 4)(*src), (c_double * 8)(*vals), _box_arr([B]),
-            two(drude["sin"]), two(drude["sout"]), c_vp(lut.data_ptr()), c_int(nid), c_double(drude["cbd"]),
-            _stream())
+            *ptrs, c_double(cbv), c_double(dbv), *geom, c_int(steps), src, vals, _box_arr([B]), two(drude["sin"]),
+            two(drude["sout"]), c_vp(lut.data_ptr()), c_int(nid), c_double(drude["cbd"]), self._tb_opts(), _stream())
         _check(rc, "tb3d_drude")
         self.launches += 1
 
@@ -1064,111 +1107,44 @@ class HipOps(HipMonitorOps):
         E, H = ("Ex", "Ey", "Ez"), ("Hx", "Hy", "Hz")
         if not (1 <= steps <= self.tb_max_steps):
             raise HipError("tb_step supports 1..%d steps per pass" % self.tb_max_steps)
-        shape = tuple(fin["Ex"].shape)
-        if self.dtype == torch.float32 and shape[2] % 4 != 0:
-            raise HipError("fp32 tb_step needs nz %% 4 == 0, got %s" % (shape,))
-        for c in E + H:
-            self._check_tensor(fin[c], shape)
-            self._check_tensor(fout[c], shape)
-            if fin[c].data_ptr() == fout[c].data_ptr():
-                raise HipError("tb_step needs distinct in/out buffers")
-            b = boxes[c]
-            for d in range(3):
-                if not _empty(b) and (b[0][d] < 0 or b[1][d] > shape[d]):
-                    raise HipError("update box %s of %s outside array %s" % (b, c, shape))
-        for d in range(3):
-            if obox[0][d] < 0 or obox[1][d] > shape[d]:
-                raise HipError("output box %s outside array %s" % (obox, shape))
-        pe = [self._cell_or_none(cb[c]) for c in E]
-        ph = [self._cell_or_none(cb[c]) for c in H]
-        percell = any(p is not None for p in pe + ph)
-        if percell:
-            cbs, cbv = self._kind_coef_args(cb, E, pe, shape)
-            dbs, dbv = self._kind_coef_args(cb, H, ph, shape)
-        else:
-            cbs = (c_vp * 3)(None, None, None)
-            dbs = (c_vp * 3)(None, None, None)
-            cbv, dbv = cb["Ex"].scalar, cb["Hx"].scalar
-            if any(cb[c].scalar != cbv for c in E) or any(cb[c].scalar != dbv for c in H):
-                raise HipError("tb_step: scalar coefficients must agree per kind")
-        src = [-1, -1, -1, -1]
-        vals = [0.0] * 8
-        if sources is not None and any(s is not None for s in sources):
-            first = next(s for s in sources if s is not None)
-            comp, idx = first[0], tuple(first[1])
-            if comp not in E:
-                raise HipError("tb_step supports E point sources only")
-            for d in range(3):
-                if not (0 <= idx[d] < shape[d]):
-                    raise HipError("source index outside array")
-            for l, s in enumerate(sources):
-                if s is None or s[0] != comp or tuple(s[1]) != idx:
-                    raise HipError("tb_step: the source must be the same point at every step")
-                vals[l] = float(s[2])
-            src = [idx[0], idx[1], idx[2], E.index(comp)]
-        arr = lambda names, f: (c_vp * 3)(*[f[c].data_ptr() for c in names])
-        if tfsf is not None and self.dtype != torch.float32:
-            # fp64 kernel with the TF/SF corrections (yee3d_tb64.hip TFS)
+        shape, percell, (cbv, dbv), ptrs, geom = self._tb3d_pass("tb_step", fin, fout, boxes, obox, cb)
+        self._check_inside("tb_step", [obox], shape, empty_too=True)
+        src, vals = self._tb_source("tb_step", sources, E, shape)
+        f32 = self.dtype == torch.float32
+        if tfsf is not None:
             sets, gtab, level0 = tfsf
-            if int(self.lib.fdtd_tfdev_size()) != 4 * sets.dev.numel():
-                raise HipError("TfDev layout mismatch")
-            self.lib.fdtd_set_tb64_shape(c_int(self.tb64_half))
-            rc = self.lib.fdtd_tb3d_tf_f64(
-                arr(E, fin), arr(H, fin), arr(E, fout), arr(H, fout), cbs, dbs, c_double(cbv), c_double(dbv),
-                c_int(shape[0]), c_int(shape[1]), c_int(shape[2]), _box_arr([boxes[c] for c in E + H]), _box_arr([obox]),
-                c_int(self.tb_xchunk), c_int(steps), (c_int * 4)(*src), (c_double * 8)(*vals), _ptr(sets.dev),
-                c_vp(gtab.data_ptr() + gtab.element_size() * level0 * sets.ld), _stream())
-            _check(rc, "tb3d_tf_f64")
-            self.launches += 1
-            return
-        if (percell and self.dtype == torch.float32 and self.tb_sparse) or tfsf is not None:
+            self._check_tfdev(sets)
+            tfp, gp = _ptr(sets.dev), c_vp(gtab.data_ptr() + gtab.element_size() * level0 * sets.ld)
+        if f32 and ((percell and self.tb_sparse) or tfsf is not None):
             # multi-row kernel with sparse per-cell coefficients / TF/SF sets
             if percell and steps > 5:
-                raise HipError("per-cell coefficients: at most 5 steps per pass")
+                raise HipError("tb_step: per-cell coefficients: at most 5 steps per pass")
+            ce = ch = None
+            ebox = hbox = ((0, 0, 0), (0, 0, 0))
             if percell:
                 ce, ebox, cbv = self._sparse_kind(cb, E, shape)
                 ch, hbox, dbv = self._sparse_kind(cb, H, shape)
-            else:
-                ce = ch = None
-                ebox = hbox = ((0, 0, 0), (0, 0, 0))
-            tfp = gp = None
-            if tfsf is not None:
-                sets, gtab, level0 = tfsf
-                tfp = _ptr(sets.dev)
-                gp = c_vp(gtab.data_ptr() + 4 * level0 * sets.ld)
-            rc = self.lib.fdtd_tb3d_ext_f32(
-                arr(E, fin), arr(H, fin), arr(E, fout), arr(H, fout), _ptr(ce), _box_arr([ebox]), _ptr(ch),
-                _box_arr([hbox]), c_double(cbv), c_double(dbv), c_int(shape[0]), c_int(shape[1]), c_int(shape[2]),
-                _box_arr([boxes[c] for c in E + H]), _box_arr([obox]), c_int(self.tb_xchunk), c_int(steps),
-                (c_int * 4)(*src), (c_double * 8)(*vals), tfp, gp, _stream())
+            if tfsf is None:
+                tfp = gp = None
+            rc = self.lib.fdtd_tb3d_ext_f32(*ptrs, _ptr(ce), _box_arr([ebox]), _ptr(ch), _box_arr([hbox]),
+                                            c_double(cbv), c_double(dbv), *geom, c_int(steps), src, vals, tfp, gp,
+                                            self._tb_opts(), _stream())
             _check(rc, "tb3d_ext")
             self.launches += 1
             return
-        if self.dtype == torch.float32:
-            self.lib.fdtd_set_tb_vec(c_int(self.tb_vec))
-            self.lib.fdtd_set_tb_rows(c_int(self.tb_rows))
-            self.lib.fdtd_set_tb_xcd(c_int(self.tb_xcd))
-            mr = self.tb_mrows
-            mr_shape = self.tb_mr_shape
-            if mr == 0 and self.tb_thin_single_row and steps <= 4 and obox[1][1] - obox[0][1] <= 8:
-                # thin y shells of a decomposed pass: 16-row tiles waste half
-                # as many rows as the 32-row multi-row tiles -- the single-row
-                # kernel's, or the multi-row kernel's 8-wave form (tb_thin_mr16)
-                if self.tb_thin_mr16:
-                    mr_shape = 2
-                else:
-                    mr = 1
-            self.lib.fdtd_set_tb_mrows(c_int(mr))
-            self.lib.fdtd_set_tb_variant(c_int(self.tb_variant))
-            self.lib.fdtd_set_tb_mr_shape(c_int(mr_shape))
+        cbs = dbs = (c_vp * 3)(None, None, None)
+        if percell:
+            cbs, cbv = self._kind_coef_args(cb, E, [self._cell_or_none(cb[c]) for c in E], shape)
+            dbs, dbv = self._kind_coef_args(cb, H, [self._cell_or_none(cb[c]) for c in H], shape)
+        args = (*ptrs, cbs, dbs, c_double(cbv), c_double(dbv), *geom, c_int(steps), src, vals)
+        if tfsf is not None:
+            # fp64 kernel with the TF/SF corrections (yee3d_tb64.hip TFS)
+            rc = self.lib.fdtd_tb3d_tf_f64(*args, tfp, gp, self._tb_opts(), _stream())
+            _check(rc, "tb3d_tf_f64")
         else:
-            self.lib.fdtd_set_tb64_shape(c_int(self.tb64_half))
-        # fp32: yee3d_tb.hip (multi-row / single-row tiles); fp64: yee3d_tb64.hip
-        rc = self.fn("tb3d_v4" if self.dtype == torch.float32 else "tb3d")(arr(E, fin), arr(H, fin), arr(E, fout), arr(H, fout), cbs, dbs, c_double(cbv),
-                                c_double(dbv), c_int(shape[0]), c_int(shape[1]), c_int(shape[2]),
-                                _box_arr([boxes[c] for c in E + H]), _box_arr([obox]), c_int(self.tb_xchunk),
-                                c_int(steps), (c_int * 4)(*src), (c_double * 8)(*vals), _stream())
-        _check(rc, "tb3d")
+            # fp32: yee3d_tb.hip (multi-row / single-row tiles); fp64: yee3d_tb64.hip
+            rc = self.fn("tb3d_v4" if f32 else "tb3d")(*args, self._tb_opts(steps, obox if f32 else None), _stream())
+            _check(rc, "tb3d")
         self.launches += 1
 
     def _tb2d_step(self, fin, fout, boxes, obox, cb, steps, sources) -> None:
@@ -1192,13 +1168,8 @@ class HipOps(HipMonitorOps):
             self._check_tensor(fout[c], shape)
             if fin[c].data_ptr() == fout[c].data_ptr():
                 raise HipError("tb_step needs distinct in/out buffers")
-            b = boxes[c]
-            for d in range(2):
-                if not _empty(b) and (b[0][d] < 0 or b[1][d] > shape[d]):
-                    raise HipError("update box %s of %s outside array %s" % (b, c, shape))
-        for d in range(2):
-            if obox[0][d] < 0 or obox[1][d] > shape[d]:
-                raise HipError("output box %s outside array %s" % (obox, shape))
+        self._check_inside("2D tb_step", [boxes[c] for c in comps], shape, nd=2)
+        self._check_inside("2D tb_step", [obox], shape, nd=2, empty_too=True)
         # per kind: per-cell arrays when any component of the kind has them,
         # else null pointers and the kind's scalar (no constant planes streamed)
         ptrs, sv = [], {}
@@ -1213,25 +1184,12 @@ class HipOps(HipMonitorOps):
                     raise HipError("tb_step: scalar coefficients must agree per kind")
         cs = (c_vp * 3)(*ptrs)
         cbv, dbv = sv["E"], sv["H"]
-        src = [-1, -1, -1]
-        vals = [0.0] * 8
-        if sources is not None and any(s is not None for s in sources):
-            first = next(s for s in sources if s is not None)
-            comp, idx = first[0], tuple(first[1])
-            if comp not in comps:
-                raise HipError("2D tb_step: source component %s not in %s" % (comp, comps))
-            if not (0 <= idx[0] < shape[0] and 0 <= idx[1] < shape[1]):
-                raise HipError("source index outside array")
-            for l, s in enumerate(sources):
-                if s is None or s[0] != comp or tuple(s[1]) != idx:
-                    raise HipError("tb_step: the source must be the same point at every step")
-                vals[l] = float(s[2])
-            src = [idx[0], idx[1], comps.index(comp)]
+        src, vals = self._tb_source("2D tb_step", sources, comps, shape, nd=2)
         two = lambda names, f: (c_vp * 2)(*([f[c].data_ptr() for c in names] + [None] * (2 - len(names))))
         rc = self.fn("tb2d")(c_int(mode), two(E, fin), two(H, fin), two(E, fout), two(H, fout), cs,
                                     c_double(cbv), c_double(dbv), c_int(shape[0]), c_int(shape[1]),
                                     _box_arr([boxes[c] for c in comps]), _box_arr([obox]), c_int(self.tb_xchunk),
-                                    c_int(steps), (c_int * 3)(*src), (c_double * 8)(*vals), _stream())
+                                    c_int(steps), src, vals, _stream())
         _check(rc, "tb2d")
         self.launches += 1
 

@@ -607,7 +607,6 @@ def amp_run(name, dut, device, dtype, shape=0, shift_abox=False, record=None):
     if hip:
         torch.cuda.synchronize()
         dut.ops.tb_mr_shape = 0
-        dut.ops.lib.fdtd_set_tb_mr_shape(0)  # (the library's global: later plain passes push their own)
     assert_unchanged(fin, keep, name)
     return dict(fout={c: fout[c].cpu() for c in COMPS}, amp=buf.cpu(), counts=counts.cpu(), sent=sent)
 
@@ -942,20 +941,30 @@ def plain_claim(family, claim):
     return (claim[0], claim[1], 1) if family == "single" else claim
 
 
-def plain_run(name, dut, device, dtype, kernel="multi"):
+def plain_run(name, dut, device, dtype, kernel="multi", record=None, **knobs):
+    """One plain pass of a case; ``knobs`` override the default tuning knobs,
+    ``record`` (a list) receives the pass's launches (``HipOps.record``).
+    ``dev`` = the device tensors (fin, fout, clones of fin): a record's
+    arguments point into them."""
     _, T, obox, _ = PLAIN[name]
-    set_knobs(dut.ops, tb_mrows=2 if kernel == "multi" else 1, tb_mr_shape=0, tb_vec=0, tb_rows=0, tb_xcd=0,
-              tb_variant=4, tb64_half=1)
+    set_knobs(dut.ops, **{**dict(tb_mrows=2 if kernel == "multi" else 1, tb_mr_shape=0, tb_vec=0, tb_rows=0, tb_xcd=0,
+                                 tb_variant=4, tb64_half=1), **knobs})
     seed = 9900 + 10 * list(PLAIN).index(name)
     Z = impedance(dut)
     fin, fout, sent, keep = run_pair_fields(live_fields(PLAIN_SIZE, seed, Z), PLAIN_SIZE, device, dtype)
     src = [("Ez", (6, 20, 3), Z * (0.5 + 0.25 * l)) for l in range(T)]
-    dut.ops.tb_step(fin, fout, drude_upd(dut), obox, dut.cb, T, src)
+    if record is not None:
+        dut.ops.record(record)
+    try:
+        dut.ops.tb_step(fin, fout, drude_upd(dut), obox, dut.cb, T, src)
+    finally:
+        if record is not None:
+            dut.ops.record(None)
     if dut.ops.name == "hip":
         torch.cuda.synchronize()
-        dut.ops.tb_mrows = 0
+        set_knobs(dut.ops, tb_mrows=0, tb_mr_shape=0, tb_variant=4)
     assert_unchanged(fin, keep, name)
-    return dict(fout={c: fout[c].cpu() for c in COMPS}, sent=sent)
+    return dict(fout={c: fout[c].cpu() for c in COMPS}, sent=sent, dev=(fin, fout, keep))
 
 
 @functools.lru_cache(None)
@@ -976,3 +985,56 @@ def test_plain_pass_sentinel(gpu, name, prec, kernel):
     bound = BOUND32 if prec == "f32" else BOUND64_PLAIN
     worst, _ = check_fields(out["fout"], plain_oracle(name)["fout"], out["sent"], DT[prec], bound, (name,))
     print("worst plain %s %s %s: %.3g of the bound" % (name, prec, kernel, worst / bound))
+
+
+def test_plain_pass_is_one_recorded_launch(gpu):
+    """A plain pass is ONE recorded launch that carries its own tile options:
+    recorded with 8 waves x 4 rows, it replays bit for bit after the object's
+    knobs changed and another HipOps object ran a pass with other knobs.
+    (Tile shapes do not change a cell's arithmetic: the bitwise comparison
+    guards the replayed arguments, the one-entry assertion the structure.)"""
+    name = "whole"
+    _, T, obox, claim = PLAIN[name]
+    assert_tiles("mr8x4", T, obox, claim)
+    dut, _ = pair(vacuum_cfg(PLAIN_SIZE, "f64"), "f32", gpu, "hip")
+    rec = []
+    first = plain_run(name, dut, gpu, torch.float32, "multi", record=rec, tb_mr_shape=1)
+    assert len(rec) == 1, [f.__name__ for f, _ in rec]
+    check_fields(first["fout"], plain_oracle(name)["fout"], first["sent"], torch.float32, BOUND32, (name, "recorded"))
+    dut.ops.tb_mr_shape, dut.ops.tb_mrows = 0, 1
+    other = copy.copy(dut)
+    other.ops = make_ops("hip", None, gpu, torch.float32)
+    assert other.ops is not dut.ops
+    plain_run("inner", other, gpu, torch.float32, "multi", tb_mr_shape=2, tb_variant=7)
+    fin, fout, keep = first["dev"]
+    for c in COMPS:
+        fout[c].copy_(to_dev(first["sent"][c], gpu, torch.float32))
+    try:
+        type(dut.ops).replay(rec)
+        torch.cuda.synchronize()
+    finally:
+        dut.ops.tb_mrows = 0
+    assert_unchanged(fin, keep, (name, "replay"))
+    for c in COMPS:
+        assert torch.equal(fout[c].cpu(), first["fout"][c]), (name, c, "the replayed pass differs from the recorded one")
+
+
+def test_passes_of_two_objects_interleave(gpu):
+    """Object A (8 waves x 4 rows, deferred stores + two planes prefetched)
+    runs a plain pass, object B (defaults) a TF/SF pass through
+    fdtd_tb3d_ext_f32, then A again: every pass runs with its own object's
+    options and meets the bound of its own test."""
+    plain, tf = "whole", "x-T1"
+    a, _ = pair(vacuum_cfg(PLAIN_SIZE, "f64"), "f32", gpu, "hip")
+    b, _ = pair(tf_cfg(TF[tf].inc), "f32", gpu, "hip")
+    assert a.ops is not b.ops
+    set_knobs(b.ops, tb_mrows=0, tb_mr_shape=0, tb_vec=0, tb_rows=0, tb_xcd=0, tb_variant=4)
+    for who in ("A", "B", "A"):
+        if who == "A":
+            out = plain_run(plain, a, gpu, torch.float32, "multi", tb_mr_shape=1, tb_variant=7)
+            want = plain_oracle(plain)
+        else:
+            out = tf_step_run(tf, b, gpu, torch.float32)
+            want = tf_step_oracle(tf)
+        worst, _ = check_fields(out["fout"], want["fout"], out["sent"], torch.float32, BOUND32, (who, plain, tf))
+        print("worst interleaved %s: %.3g of the bound" % (who, worst / BOUND32))
