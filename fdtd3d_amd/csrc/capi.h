@@ -249,4 +249,13 @@ int fdtd_farfield_ent_size();
 int fdtd_energy_eval_f32(const void* tab, int n, int nblocks, int rows_blk, int R, void* partials, void* out, void* s);
 int fdtd_energy_eval_f64(const void* tab, int n, int nblocks, int rows_blk, int R, void* partials, void* out, void* s);
 int fdtd_energy_ent_size();
+
+// one sample of a probe monitor (probe_kernels.hip): tab = nslots device
+// entries of fdtd_probe_ent_size() bytes (field array, element offset), series
+// = capacity x nslots device doubles; slot s of row `row` = the slot's element
+// widened to fp64.  hipErrorInvalidValue for a row outside [0, capacity), a
+// negative nslots or a null pointer; nslots == 0 launches nothing
+int fdtd_probe_sample_f32(const void* tab, int nslots, void* series, int row, int capacity, void* s);
+int fdtd_probe_sample_f64(const void* tab, int nslots, void* series, int row, int capacity, void* s);
+int fdtd_probe_ent_size();
 }

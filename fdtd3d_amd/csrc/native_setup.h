@@ -643,9 +643,10 @@ bool native_supported(const fdtd::Settings& s) {
   // (parallel grids: the gathered grid in the serial form, scattered over the ranks on resume)
   const bool ckpt_ok = !ckpt || (!s.doUsePML && !s.doUseTFSF && !s.doUseMetamaterials && !s.doUseAmplitudeMode &&
                                  !s.doUseNTFF && (!s.doUseParallelGrid || s.dimension == 3));
-  // running-DFT, flux, far-field and energy monitors (models/dft.py, models/flux.py, models/farfield.py,
-  // models/energy.py) exist in the Python driver only
-  if (s.doUseDft || s.doUseNtffDft || s.doUseFlux || s.doUseFarfield || s.doUseEnergy || s.stopDecayBy != 0.0)
+  // running-DFT, flux, far-field and energy monitors and field probes (models/dft.py, models/flux.py,
+  // models/farfield.py, models/energy.py, models/probe.py) exist in the Python driver only
+  if (s.doUseDft || s.doUseNtffDft || s.doUseFlux || s.doUseFarfield || s.doUseEnergy || s.stopDecayBy != 0.0 ||
+      s.doUseProbes)
     return false;
   return !((s.doUsePML && !cpml_ok && !upml_ok) || (s.doUseTFSF && !tfsf_ok) || !meta_ok || !ntff_ok || !amp_ok ||
            !par_ok || !ckpt_ok || s.doUseDoubleMaterialPrecision ||

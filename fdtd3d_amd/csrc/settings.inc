@@ -180,5 +180,15 @@ FDTD_ACTION ("--same-size-energy", "Copy the x energy box distance to y and z")
 FDTD_INT (energyStep, "--energy-step", 0, "Steps between energy samples; 0 = automatic (a multiple of the blocked pass length or of the DFT / flux sampling step, at least 50)")
 FDTD_INT (energyStart, "--energy-start", 0, "First step at which the energy monitor samples")
 FDTD_FLOAT (stopDecayBy, "--stop-decay-by", 0.0, "Stop the run once the source has ended and the field energy in the box has fallen to this fraction of its peak (--time-steps stays the upper bound; pulsed sources only); 0 = off; implies --use-energy")
+/* ---- extensions: field probes, time series and spectra at points (models/probe.py; Python driver) ---- */
+FDTD_BOOL (doUseProbes, "--use-probes", "Record the fields at the --probe-points as time series, sampled between passes: points, samples and spectrum in the --json line, one text table per point with --save-res")
+FDTD_STRING (probePoints, "--probe-points", "", "Probe points as global cell indices, x,y,z;x,y,z;... (x,y in 2D, x in 1D)")
+FDTD_STRING (probeFile, "--probe-file", "", "File with further probe points, one per line: indices separated by commas or blanks, # starts a comment")
+FDTD_STRING (probeComponents, "--probe-components", "", "Recorded field components, comma separated; empty = every component of the scheme")
+FDTD_STRING (probePosition, "--probe-position", "node", "Where a component is taken: node (its own Yee sample at the index, an exact copy) or centre (the mean of its 1, 2 or 4 samples around the cell centre)")
+FDTD_INT (probeStep, "--probe-step", 0, "Steps between probe samples; 0 = automatic (the blocked pass length, or the sampling step of the DFT / flux / far-field / energy monitors: no pass is cut)")
+FDTD_INT (probeStart, "--probe-start", 0, "First step at which the probes sample")
+FDTD_INT (probeSpectrum, "--probe-spectrum", 0, "Report the spectrum of the probe series at this many wavelengths, evenly spaced in frequency over --probe-band (with --source gaussian divided by the source signal's spectrum); 0 = none")
+FDTD_STRING (probeBand, "--probe-band", "", "Band of --probe-spectrum as free-space wavelengths lo,hi (m)")
 FDTD_BOOL (doPrintJson, "--json", "Print a JSON summary line after the run")
 FDTD_INT (warmupSteps, "--warmup-steps", 0, "Untimed time steps run before the timed loop (benchmarking; they advance the simulation)")

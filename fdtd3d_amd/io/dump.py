@@ -232,6 +232,25 @@ def dump_materials(scheme, settings, directory: Optional[str] = None) -> List[st
     return files
 
 
+def dump_probes(monitor, series, step: int, directory: str) -> List[str]:
+    """The series of a probe monitor (models/probe.py; ``series`` = what its
+    ``series()`` returned) as one text table per point,
+    ``probe<p>_[timestep=<step>].txt``: a header line, then one row ``step
+    t_E t_H <components>`` per sample (seconds; E and H sample times)."""
+    import os
+    files: List[str] = []
+    te, th = (t.tolist() for t in monitor.times())
+    for p, point in enumerate(monitor.points):
+        path = os.path.join(directory, "probe%d_[timestep=%d].txt" % (p, step))
+        with open(path, "w") as f:
+            f.write("# point %s (%s): step t_E t_H %s\n" % (" ".join("%d" % v for v in point), monitor.position,
+                                                           " ".join(monitor.comps)))
+            for n, t in enumerate(monitor.steps):
+                f.write("%d %.17g %.17g %s\n" % (t, te[n], th[n], " ".join("%.17g" % float(v) for v in series[n, p])))
+        files.append(path)
+    return files
+
+
 def dump_farfield(result, wavelengths, step: int, directory: str) -> List[str]:
     """The far-field pattern of a monitor (models/farfield.py ``evaluate``) as
     one text table per wavelength, ``farfield<k>_[timestep=<step>].txt``: a

@@ -153,6 +153,34 @@ def monitors_from_config(scheme) -> Dict[str, "DftMonitor"]:
     return out
 
 
+class SourceDft:
+    """Running DFT of the source signal at the angular frequencies ``omegas``
+    over a monitor's samples: what a spectrum is divided by to be one of the
+    system and not of the pulse (models/surface.py ``incident``, models/
+    probe.py ``spectrum``).  Host floats, one ``add`` per sample."""
+
+    def __init__(self, omegas: Sequence[float]):
+        self.omegas = [float(w) for w in omegas]
+        self.acc = [[0.0, 0.0] for _ in self.omegas]
+        self.n = 0
+
+    def add(self, scheme, t: int) -> None:
+        """The sample after step ``t``: the value the source gave E in that
+        step, ``source_value(t - 1)``, at the E sample time ``(t - 1) dt``."""
+        te = (t - 1) * scheme.dt
+        v = scheme.source_value(t - 1, 0)
+        for acc, w in zip(self.acc, self.omegas):
+            acc[0] += v * math.cos(w * te)
+            acc[1] += v * math.sin(w * te)
+        self.n += 1
+
+    def phasors(self) -> List[complex]:
+        """``(2 / N) (Re + i Im)`` per frequency (:meth:`DftMonitor.phasor`'s
+        convention)."""
+        scale = 2.0 / max(1, self.n)
+        return [complex(re * scale, im * scale) for re, im in self.acc]
+
+
 class DftMonitor:
     """Running DFT of ``requests`` = [(component, global index box)] at
     ``wavelengths`` (free-space, metres), sampled after every step ``t >=

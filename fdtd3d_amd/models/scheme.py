@@ -135,6 +135,15 @@ class SchemeConfig:
     energy_step: int = 0                     # steps between samples; 0 = automatic (models/energy.py auto_step)
     energy_start: int = 0
     stop_decay_by: float = 0.0               # stop once the energy is this fraction of its peak; 0 = off
+    use_probes: bool = False                 # field probes: time series at points (models/probe.py)
+    probe_points: str = ""                   # "x,y,z;x,y,z;..." global cell indices
+    probe_file: str = ""                     # further points, one per line
+    probe_components: str = ""               # comma separated; empty = every component of the scheme
+    probe_position: str = "node"             # node (the Yee sample at the index) | centre (mean around the centre)
+    probe_step: int = 0                      # steps between samples; 0 = automatic (models/probe.py auto_step)
+    probe_start: int = 0
+    probe_spectrum: int = 0                  # wavelengths of the reported spectrum, even in frequency; 0 = none
+    probe_band: str = ""                     # "lo,hi" metres
 
     @classmethod
     def from_settings(cls, s) -> "SchemeConfig":
@@ -176,7 +185,10 @@ class SchemeConfig:
                 (s.farfieldSizeX, s.farfieldSizeY, s.farfieldSizeZ), (s.ntffSizeX, s.ntffSizeY, s.ntffSizeZ))),
             farfield_ntheta=s.farfieldNTheta, farfield_nphi=s.farfieldNPhi,
             use_energy=s.doUseEnergy or s.stopDecayBy > 0, energy_size=(s.energySizeX, s.energySizeY, s.energySizeZ),
-            energy_step=s.energyStep, energy_start=s.energyStart, stop_decay_by=s.stopDecayBy)
+            energy_step=s.energyStep, energy_start=s.energyStart, stop_decay_by=s.stopDecayBy,
+            use_probes=s.doUseProbes, probe_points=s.probePoints, probe_file=s.probeFile,
+            probe_components=s.probeComponents, probe_position=s.probePosition, probe_step=s.probeStep,
+            probe_start=s.probeStart, probe_spectrum=s.probeSpectrum, probe_band=s.probeBand)
 
 
 def _drude_coefs(dt: float, e0: float, eps, w, g, q: float):

@@ -8,14 +8,13 @@ running DFT of the source signal, and the placement against the TF/SF box.
 
 from __future__ import annotations
 
-import math
 from typing import Optional, Sequence
 
 import torch
 
 from ..ops.dft import FluxOperand, acc_shape, vec_width, z_pad
 from ..utils.assertions import FdtdError
-from .dft import DftMonitor
+from .dft import DftMonitor, SourceDft
 from .ntff import ETA0, _faces, _plan_box, ntff_requests
 
 TFSF_MIN_DISTANCE = 2  # cells between a box face and the TF/SF face: the averages must not straddle it
@@ -95,8 +94,7 @@ class SurfaceMonitor:
         self.dft = dft
         self.wavelengths, self.omegas = dft.wavelengths, dft.omegas
         self.step, self.start = dft.step, dft.start
-        self._n_src = 0
-        self._src = [[0.0, 0.0] for _ in self.wavelengths]  # running DFT of the source signal
+        self._source = SourceDft(self.omegas)  # running DFT of the source signal
         self._terms = None
         if register:
             scheme.add_periodic(self.step, self.start % self.step, self.sample)
@@ -104,6 +102,10 @@ class SurfaceMonitor:
     @property
     def samples(self) -> int:
         return self.dft.samples
+
+    @property
+    def _n_src(self) -> int:
+        return self._source.n
 
     def _placement(self, cfg) -> str:
         """``none`` without TF/SF, else ``inside`` or ``outside`` the TF/SF
@@ -130,12 +132,7 @@ class SurfaceMonitor:
             return
         if not self.shared:
             self.dft.sample(scheme, t)
-        te = self.dft.sample_times(scheme, t)[0]
-        v = scheme.source_value(t - 1, 0)
-        for acc, w in zip(self._src, self.omegas):
-            acc[0] += v * math.cos(w * te)
-            acc[1] += v * math.sin(w * te)
-        self._n_src += 1
+        self._source.add(scheme, t)
 
     def incident(self) -> torch.Tensor:
         """(K,) ``|A_src|^2 / (2 eta0)`` in W / m^2, ``A_src`` the phasor of
@@ -143,8 +140,8 @@ class SurfaceMonitor:
         the sine source over whole periods, the pulse spectrum for a Gaussian
         source."""
         n = max(1, self._n_src)
-        return torch.tensor([((2.0 / n) ** 2) * (re * re + im * im) / (2.0 * ETA0) for re, im in self._src],
-                            dtype=torch.float64)
+        return torch.tensor([((2.0 / n) ** 2) * (re * re + im * im) / (2.0 * ETA0)
+                             for re, im in self._source.acc], dtype=torch.float64)
 
     # --------------------------------------------------------------------- terms
     def _operand(self, comp: str, plan, gathered: bool) -> Optional[FluxOperand]:

@@ -1,6 +1,7 @@
 """The monitor operations of the HIP backend, a mixin of
-:class:`~.hip_ops.HipOps`: ``dft_accumulate``, ``dft_flux``, ``dft_farfield``
-and ``field_sumsq`` (csrc/dft_, flux_, farfield_, energy_kernels.hip).  Each
+:class:`~.hip_ops.HipOps`: ``dft_accumulate``, ``dft_flux``, ``dft_farfield``,
+``field_sumsq`` and ``probe_sample`` (csrc/dft_, flux_, farfield_, energy_,
+probe_kernels.hip).  Each
 runs from a device table of fixed-size entries, built once per monitor (and
 set of arrays) and cached on its entries / terms; the builders validate all
 the kernels rely on, which check nothing beyond their boxes.
@@ -15,6 +16,7 @@ from .dft import (DFT_ENT_SIZE, DFT_MAX_K, FAR_ENT_SIZE, FAR_GROUP, FAR_SLOTS, F
                   z_pad)
 from .energy import ENERGY_ENT_SIZE
 from .hip_lib import HipError, _check, _ptr, _stream, c_double, c_int
+from .probe import PROBE_ENT_SIZE
 
 
 def _ent_table(n: int, size: int):
@@ -391,3 +393,59 @@ class HipMonitorOps:
         _check(rc, "energy_eval")
         self.launches += 2 if nblocks else 1
         return out
+
+    # --------------------------------------------------------- probe monitors
+    PROBE_MAX_TABLES = 4  # cached device tables per monitor (the F / F_alt ping-pong needs 2)
+
+    def _probe_table(self, entries):
+        """The device table of a monitor's slots with their current field
+        arrays (None without slots); every array and offset checked."""
+        self._check_ent_size("Probe", "probe", PROBE_ENT_SIZE)
+        item = 16 // vec_width(self.dtype)
+        for f in entries.fields:
+            self._check_tensor(f)
+            if f.device != entries.series.device:
+                raise HipError("probe_sample: array on %s, series on %s" % (f.device, entries.series.device))
+            if f.data_ptr() % item:
+                raise HipError("probe_sample: field array not aligned to its element size")
+        why = entries.offset_error()
+        if why:
+            raise HipError("probe_sample: " + why)
+        if len(entries) >= 2 ** 31 - 256:
+            raise HipError("probe_sample: too many slots for one launch")
+        if not len(entries):
+            return None
+        e64, _, _ = _ent_table(len(entries), PROBE_ENT_SIZE)
+        for s, (fi, off) in enumerate(entries.rows):
+            e64[s, 0] = entries.fields[fi].data_ptr()
+            e64[s, 1] = off
+        return torch.from_numpy(e64).to(self.device)
+
+    def probe_sample(self, entries, row: int) -> None:
+        """One sample of a probe monitor (ops/probe.py ``ProbeEntries``) in
+        ONE launch over all its slots (probe_kernels.hip k_probe_sample): row
+        ``row`` of ``entries.series`` = every slot's element, widened to fp64,
+        ``row`` passed by value.  Everything is validated before the launch.
+        The device table is cached on ``entries`` per set of field arrays (F /
+        F_alt ping-pong: the current arrays are looked up at every call)."""
+        row = int(row)
+        if not 0 <= row < entries.capacity:
+            raise HipError("probe_sample: row %d of %d" % (row, entries.capacity))
+        series = entries.series
+        if (series.device.type != "cuda" or series.dtype != torch.float64 or not series.is_contiguous()
+                or tuple(series.shape) != (entries.capacity, len(entries))):
+            raise HipError("probe_sample: series of %d x %d float64 on the device, got %s %s on %s"
+                           % (entries.capacity, len(entries), tuple(series.shape), series.dtype, series.device))
+        key = tuple((f.data_ptr(), f.numel(), f.dtype, f.device, f.is_contiguous()) for f in entries.fields)
+        tab = entries.tables.get(key, False)
+        if tab is False:
+            tab = self._probe_table(entries)
+            if len(entries.tables) >= self.PROBE_MAX_TABLES:
+                entries.tables.clear()  # reallocated field arrays: drop the tables of the old ones
+            entries.tables[key] = tab
+        if tab is None:
+            return
+        rc = self.fn("probe_sample")(_ptr(tab), c_int(len(entries)), _ptr(series), c_int(row),
+                                     c_int(entries.capacity), _stream())
+        _check(rc, "probe_sample")
+        self.launches += 1

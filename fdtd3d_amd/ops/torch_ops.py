@@ -657,6 +657,35 @@ class TorchOps:
             out[e.row] += e.field[x0:x1, y0:y1, z0:z1].double().square().sum()
         return out
 
+    def probe_sample(self, entries, row: int) -> None:
+        """One sample of a probe monitor (ops/probe.py ``ProbeEntries``): row
+        ``row`` of ``entries.series`` = every slot's element, widened to
+        fp64; the other rows stay as they are.  The oracle of csrc/
+        probe_kernels.hip."""
+        if not 0 <= int(row) < entries.capacity:
+            raise ValueError("probe_sample: row %d of %d" % (row, entries.capacity))
+        why = entries.offset_error()
+        if why:
+            raise ValueError("probe_sample: " + why)
+        series = entries.series
+        if tuple(series.shape) != (entries.capacity, len(entries)) or series.dtype != torch.float64:
+            raise ValueError("probe_sample: series of shape %s %s" % (tuple(series.shape), series.dtype))
+        plan = entries.tables.get("torch")  # per array: its slots' columns and offsets (``add`` drops it)
+        if plan is None:
+            plan = []
+            for fi in range(len(entries.fields)):
+                cols = [s for s, (i, _) in enumerate(entries.rows) if i == fi]
+                if cols:
+                    plan.append((fi, torch.tensor(cols, dtype=torch.int64, device=series.device),
+                                 torch.tensor([entries.rows[s][1] for s in cols], dtype=torch.int64,
+                                              device=series.device)))
+            entries.tables["torch"] = plan
+        for fi, cols, offs in plan:
+            f = entries.fields[fi]
+            if not f.is_contiguous():
+                raise ValueError("probe_sample: contiguous field arrays")
+            series[int(row), cols] = f.reshape(-1)[offs].double()
+
 
 class TfsfTable:
     """Per-component TF/SF correction list: ``target[off] += coef *

@@ -164,14 +164,17 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         return status
     log.set_level(settings.logLevel)
     if (settings.doUseDft or settings.doUseNtffDft or settings.doUseFlux or settings.doUseFarfield
-            or settings.doUseEnergy or settings.stopDecayBy != 0):
-        # refused before anything is set up, never a silent fallback (models/dft.py, models/energy.py)
+            or settings.doUseEnergy or settings.stopDecayBy != 0 or settings.doUseProbes):
+        # refused before anything is set up, never a silent fallback (models/dft.py, models/energy.py,
+        # models/probe.py)
         from .models.dft import refuse_config
         from .models.energy import refuse_energy_config
+        from .models.probe import refuse_probe_config
         from .models.scheme import SchemeConfig
         cfg0 = SchemeConfig.from_settings(settings)
         ckpt = bool(settings.checkpointDir or settings.loadFromFile)
-        why = refuse_config(cfg0, checkpoints=ckpt) or refuse_energy_config(cfg0, checkpoints=ckpt)
+        why = (refuse_config(cfg0, checkpoints=ckpt) or refuse_energy_config(cfg0, checkpoints=ckpt)
+               or refuse_probe_config(cfg0, checkpoints=ckpt))
         if why:
             out.write("ERROR: %s\n" % why)
             return EXIT_ERROR
@@ -266,6 +269,18 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
             # one line per sample (reads that sample alone to the host)
             scheme.add_periodic(energy.step, energy.start % energy.step,
                                 lambda s, t: energy.report_sample(energy_out) if t >= energy.start else None)
+    probes = None
+    if scheme.cfg.use_probes:
+        from .models.probe import band_wavelengths, probes_from_config
+        from .utils.assertions import FdtdError
+        try:
+            # after every other monitor: the automatic step follows theirs (models/probe.py)
+            probes = probes_from_config(scheme)
+        except FdtdError as e:
+            out.write("ERROR: %s\n" % e)
+            if dist is not None:
+                dist.destroy_process_group()
+            return EXIT_ERROR
     steps = max(0, settings.numTimeSteps - start_step)
 
     def sync():
@@ -328,6 +343,23 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
             out.write("WARNING: --stop-decay-by %g not reached within --time-steps %d: field energy %.6g of its peak "
                       "at step %d (a static residue or the absorber's reflection can floor the decay)\n"
                       % (energy.decay_by, settings.numTimeSteps, energy_result["ratio"], scheme.t))
+    probes_info = None
+    if probes is not None:
+        # every rank: a decomposed run collects the series on rank 0 (None elsewhere)
+        series = probes.series()
+        if series is not None:
+            spec, wl = None, []
+            pulsed = scheme.cfg.source == "gaussian"  # a spectrum of the system: divided by the pulse's
+            if scheme.cfg.probe_spectrum > 0 and probes.samples:
+                wl = band_wavelengths(scheme.cfg.probe_spectrum, scheme.cfg.probe_band)
+                spec = probes.spectrum(wl, normalise=pulsed, series=series)
+            probes_info = probes.info(spec, wl, pulsed)
+            out.write("=== probes t=%u: %d points x %d components (%s), %d samples every %d steps from step %d\n"
+                      % (scheme.t, len(probes.points), len(probes.comps), probes.position, probes.samples,
+                         probes.step, probes.start))
+            if settings.doSaveRes:
+                from .io.dump import dump_probes
+                dump_probes(probes, series, scheme.t, settings.outputDir)
     if settings.checkpointDir:
         save_checkpoint(scheme, settings.checkpointDir)
     phases = scheme.prof.summary() if scheme.prof.enabled else None
@@ -361,6 +393,8 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                 rec["farfield"] = farfield.info(farfield_result)
             if energy_result is not None:
                 rec["energy"] = energy.info(energy_result)
+            if probes_info is not None:
+                rec["probes"] = probes_info
             if breakdown is not None:
                 rec["rank0_passes"] = breakdown  # decomposed passes: interior / exchange wait / shell ms
             if scheme.device.type == "cuda":

@@ -261,6 +261,8 @@ class Settings:
             raise SettingsError("--source must be sine or gaussian")
         if self.dftHTime not in ("half", "same"):
             raise SettingsError("--dft-h-time must be half or same")
+        if self.probePosition not in ("node", "centre"):
+            raise SettingsError("--probe-position must be node or centre")
         if self.bufferSize < 1:
             raise SettingsError("--buffer-size must be >= 1")
         for n in ("sizeX", "sizeY", "sizeZ"):
