@@ -1,4 +1,5 @@
-// Host-side native runtime: topology optimiser, Yee ranges, DAT/BMP output.
+// Host-side native runtime: topology optimiser, Yee ranges, DAT/BMP output,
+// hybrid pass geometry, chain / plain regions of 3D UPML / dispersive runs.
 #include "host_native.h"
 
 #include <algorithm>
@@ -229,6 +230,44 @@ bool hybrid_windows(const Box6& alloc, const Box6& K, const Box6& Dm, int T, con
     if (!empty6(w)) copy.push_back(w);
   }
   return true;
+}
+
+// ---- chain / plain regions ----
+Box6 dispersive_box(const Int3& size, const double* ctr, double radius) {
+  Box6 b;
+  for (int a = 0; a < 3; ++a) {
+    b[a] = std::max(0, (int)std::floor(ctr[a] - radius) - 2);
+    b[3 + a] = std::min(size[a], (int)std::ceil(ctr[a] + radius) + 3);
+  }
+  return b;
+}
+
+ChainRegions chain_regions(const Int3& size, const int* pml, bool use_pml, bool has_dbox, const Box6& dbox) {
+  ChainRegions R;
+  const Box6 whole = {0, 0, 0, size[0], size[1], size[2]};
+  Box6 inner = whole;
+  for (int a = 0; a < 3 && use_pml; ++a) {
+    inner[a] = pml[a] + 1;
+    inner[3 + a] = size[a] - pml[a] - 1;
+  }
+  const bool cut = has_dbox && !empty6(dbox);
+  bool inside = !empty6(inner);
+  for (int a = 0; a < 3 && cut; ++a) inside = inside && dbox[a] >= inner[a] && dbox[3 + a] <= inner[3 + a];
+  if (!inside) {
+    R.chain.push_back(whole);
+    R.disp.push_back(true);
+    return R;
+  }
+  if (use_pml) R.chain = box_minus6(whole, inner);
+  R.disp.assign(R.chain.size(), false);
+  if (cut) {
+    R.chain.push_back(dbox);
+    R.disp.push_back(true);
+    R.plain = box_minus6(inner, dbox);
+  } else {
+    R.plain.push_back(inner);
+  }
+  return R;
 }
 
 }  // namespace fdtd

@@ -1,5 +1,6 @@
 // Host-side native runtime pieces shared by the standalone driver:
-// topology optimiser, Yee computation ranges, DAT/BMP writers.
+// topology optimiser, Yee computation ranges, hybrid pass geometry, the chain /
+// plain region plan of 3D UPML runs, DAT/BMP writers.
 #pragma once
 
 #include <array>
@@ -33,6 +34,22 @@ using Box6 = std::array<int, 6>;
 std::vector<Box6> box_minus6(const Box6& a, const Box6& b);  // non-empty slabs: x low / high, y, z
 bool hybrid_windows(const Box6& alloc, const Box6& K, const Box6& Dm, int T, const bool* act, const Int3& size,
                     std::vector<std::vector<Box6>>& shells, std::vector<Box6>& copy);
+
+// ---- chain / plain regions of a 3D UPML or dispersive run (models/scheme.py _init_chain_regions) ----
+// The D/B chain runs only where it differs from the plain update: the PML
+// slabs (one cell of staggering slack: whole minus the inner box) and the
+// dispersive sphere's box; the plain kernels run on the rest.  `chain` lists
+// the slabs (x low / high, then y, then z; disp false), then the dispersive
+// box (disp true); `plain` the inner box, or its slabs around the dispersive
+// box.  A dispersive box that reaches the slabs (or an inner box that
+// vanishes) makes the whole grid one dispersive chain region.
+struct ChainRegions {
+  std::vector<Box6> chain, plain;
+  std::vector<bool> disp;  // per chain region: holds dispersive cells
+};
+// bounding box of the sphere's smoothed cells with the stencils' reach, clamped to the grid
+Box6 dispersive_box(const Int3& size, const double* ctr, double radius);
+ChainRegions chain_regions(const Int3& size, const int* pml, bool use_pml, bool has_dbox, const Box6& dbox);
 
 // ---- files (reference naming, Source/File-Management/Commons.h:56-68) ----
 std::string grid_file_name(long step, int rank, const std::string& name, const std::string& dir);

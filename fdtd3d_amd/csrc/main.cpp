@@ -54,12 +54,14 @@
 #include "native_ckpt.h"
 #include "native_amp.h"
 #include "native_lowdim.h"
+#include "native_step.h"
 #include "native_run.h"
 
 namespace {
 
 
-// one GPU: the stages of native_run.h (set-up, pass plans, the run loop, the report)
+// one GPU: the stages of native_run.h (set-up, pass plans, the timed run, the report) on the
+// stepped path of native_step.h
 template <typename T>
 int run(const fdtd::Settings& s) {
   if (s.doUseComplexFieldValues) {

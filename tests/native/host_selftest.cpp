@@ -2,8 +2,10 @@
 // by tests/test_native_cpu.py::test_host_runtime_under_sanitizers (the
 // reference's only guards were ASSERT + backtrace, Source/Helpers/Assert.h:25-91).
 // Exercises the settings parser (every option kind, cmd-file round trip, bad
-// input), the topology optimiser, chunk bounds, file naming and the DAT / BMP
-// writers; exits non-zero on the first failed check.
+// input), the topology optimiser, chunk bounds, the chain / plain region plan
+// of 3D UPML / dispersive runs, file naming and the DAT / BMP writers; exits
+// non-zero when a check failed.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -21,8 +23,89 @@ static int g_fail = 0;
     }                                                              \
   } while (0)
 
+using fdtd::Box6;
+
+static long long vol6(const Box6& b) {
+  if (b[3] <= b[0] || b[4] <= b[1] || b[5] <= b[2]) return 0;
+  return (long long)(b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]);
+}
+
+// chain + plain regions: pairwise disjoint, volumes summing to the grid's
+static void check_partition(const fdtd::ChainRegions& R, const fdtd::Int3& n) {
+  std::vector<Box6> all = R.chain;
+  all.insert(all.end(), R.plain.begin(), R.plain.end());
+  long long sum = 0;
+  for (size_t p = 0; p < all.size(); ++p) {
+    CHECK(vol6(all[p]) > 0);
+    sum += vol6(all[p]);
+    for (size_t q = p + 1; q < all.size(); ++q) {
+      Box6 c;
+      for (int a = 0; a < 3; ++a) {
+        c[a] = std::max(all[p][a], all[q][a]);
+        c[3 + a] = std::min(all[p][3 + a], all[q][3 + a]);
+      }
+      CHECK(vol6(c) == 0);
+    }
+  }
+  CHECK(sum == (long long)n[0] * n[1] * n[2]);
+  CHECK(R.disp.size() == R.chain.size());
+}
+
+// fdtd::chain_regions on a 40^3 grid with a sphere at the centre: the four
+// region plans of a 3D UPML / dispersive run, expected boxes derived by hand
+static void check_chain_regions() {
+  const fdtd::Int3 n = {40, 40, 40};
+  const int pml[3] = {10, 10, 10};
+  const double ctr[3] = {20.0, 20.0, 20.0};
+  const Box6 none = {0, 0, 0, 0, 0, 0};
+  // the six slabs of [0, 40)^3 minus [11, 29)^3: x low / high, then y, then z
+  const std::vector<Box6> shell = {{0, 0, 0, 11, 40, 40},   {29, 0, 0, 40, 40, 40},   {11, 0, 0, 29, 11, 40},
+                                   {11, 29, 0, 29, 40, 40}, {11, 11, 0, 29, 29, 11}, {11, 11, 29, 29, 29, 40}};
+  const Box6 inner = {11, 11, 11, 29, 29, 29};
+  {  // A: PML 10 and a radius-5 sphere: its box [13, 28)^3 lies inside the inner box
+    const Box6 d = fdtd::dispersive_box(n, ctr, 5.0);
+    CHECK((d == Box6{13, 13, 13, 28, 28, 28}));
+    const fdtd::ChainRegions R = fdtd::chain_regions(n, pml, true, true, d);
+    CHECK(R.chain.size() == 7 && R.plain.size() == 6);
+    for (size_t q = 0; q < 6 && q < R.chain.size(); ++q) CHECK(R.chain[q] == shell[q] && !R.disp[q]);
+    CHECK(R.chain.back() == d && R.disp.back());
+    const std::vector<Box6> rest = {{11, 11, 11, 13, 29, 29}, {28, 11, 11, 29, 29, 29}, {13, 11, 11, 28, 13, 29},
+                                    {13, 28, 11, 28, 29, 29}, {13, 13, 11, 28, 28, 13}, {13, 13, 28, 28, 28, 29}};
+    CHECK(R.plain == rest);
+    check_partition(R, n);
+  }
+  {  // B: radius 8: the box starts at 10, below the inner box's 11 -- one dispersive chain region, the grid
+    const Box6 d = fdtd::dispersive_box(n, ctr, 8.0);
+    CHECK(d[0] == 10 && d[3] == 31);
+    const fdtd::ChainRegions R = fdtd::chain_regions(n, pml, true, true, d);
+    CHECK(R.chain.size() == 1 && R.plain.empty());
+    CHECK((R.chain[0] == Box6{0, 0, 0, 40, 40, 40}) && R.disp[0]);
+    check_partition(R, n);
+  }
+  {  // C: no PML, the radius-5 sphere: the chain is its box, the plain update on the six slabs around it
+    const Box6 d = fdtd::dispersive_box(n, ctr, 5.0);
+    const fdtd::ChainRegions R = fdtd::chain_regions(n, pml, false, true, d);
+    CHECK(R.chain.size() == 1 && R.chain[0] == d && R.disp[0]);
+    const std::vector<Box6> rest = {{0, 0, 0, 13, 40, 40},   {28, 0, 0, 40, 40, 40},   {13, 0, 0, 28, 13, 40},
+                                    {13, 28, 0, 28, 40, 40}, {13, 13, 0, 28, 28, 13}, {13, 13, 28, 28, 28, 40}};
+    CHECK(R.plain == rest);
+    check_partition(R, n);
+  }
+  {  // D: PML only: the six slabs, none dispersive, and the inner box on the plain update
+    const fdtd::ChainRegions R = fdtd::chain_regions(n, pml, true, false, none);
+    CHECK(R.chain == shell);
+    for (bool f : R.disp) CHECK(!f);
+    CHECK(R.plain.size() == 1 && R.plain[0] == inner);
+    check_partition(R, n);
+  }
+  // the dispersive box is clamped to the grid
+  const double corner[3] = {1.0, 20.0, 39.0};
+  CHECK((fdtd::dispersive_box(n, corner, 5.0) == Box6{0, 13, 32, 9, 28, 40}));
+}
+
 int main(int argc, char** argv) {
   const std::string dir = argc > 1 ? argv[1] : ".";
+  check_chain_regions();
   {
     fdtd::Settings s;
     const char* a[] = {"fdtd3d", "--3d", "--sizex", "64", "--same-size", "--use-pml", "--pml-type", "cpml",
