@@ -106,6 +106,7 @@ int main(int argc, char** argv) {
                  "grids with NTFF in 2D, checkpoints beyond plain media, running-DFT, flux and far-field monitors (--use-dft, --ntff-dft, --use-flux, --use-farfield), "
                  "the energy monitor and its decay-based stop (--use-energy, --stop-decay-by), "
                  "field probes (--use-probes), "
+                 "file scenes (--scene file), "
                  "and complex fields with amplitude mode, "
                  "NTFF, checkpoints or parallel grids run through the Python driver: python -m fdtd3d_amd <same options>\n");
     return 2;

@@ -648,6 +648,8 @@ bool native_supported(const fdtd::Settings& s) {
   if (s.doUseDft || s.doUseNtffDft || s.doUseFlux || s.doUseFarfield || s.doUseEnergy || s.stopDecayBy != 0.0 ||
       s.doUseProbes)
     return false;
+  // file scenes (layout/scene_file.py, the scene_sample op) too
+  if (s.scene == "file" || !s.sceneFile.empty()) return false;
   return !((s.doUsePML && !cpml_ok && !upml_ok) || (s.doUseTFSF && !tfsf_ok) || !meta_ok || !ntff_ok || !amp_ok ||
            !par_ok || !ckpt_ok || s.doUseDoubleMaterialPrecision ||
            // complex fields: two real planes of one-GPU runs (main.cpp run)

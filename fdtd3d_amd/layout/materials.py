@@ -22,18 +22,23 @@ Scenes:
 * ``drude-sphere`` -- one electric Drude sphere (eps_inf = 1, omega_p =
   sqrt(2)*2*pi*f as in the reference scene, gamma = 0) at ``--sphere-center-*``
   with ``--sphere-radius``, in vacuum (BASELINE config 4).
+* ``file`` -- user-defined boxes, spheres and cylinders painted over vacuum
+  (``--scene-file``; :mod:`.scene_file`).  Such a scene is never evaluated on
+  an eps-layout grid: the backend's ``scene_sample`` op writes each component's
+  averaged material directly.
 """
 
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .approximation import approximate_drude, approximate_material, approximate_sphere
+from .scene_file import build_table, check_scheme, load_scene_file, parse_objects
 from .yee import MATERIAL_STENCIL, MATERIAL_STENCIL_DOUBLE, YeeLayout
 
 SQRT2_F32 = float(np.float32(np.sqrt(np.float32(2.0))))  # reference uses sqrtf(2.0)
@@ -47,6 +52,38 @@ class Scene:
     sphere_eps: float = 2.0
     sphere_radius: float = 20.0
     sphere_center: Tuple[float, float, float] = (40.5, 40.5, 40.5)
+    objects: Optional[Sequence] = None   # kind "file": dictionaries of the scene-file format, painted in order
+    smoothing: str = "linear"            # kind "file": linear | none
+
+    def __post_init__(self):
+        if self.kind == "file":
+            # refused here, before anything is allocated (ValueError with a message)
+            self.objects = parse_objects(list(self.objects or ()), self.smoothing)
+            check_scheme(self.objects, self.scheme)
+            self._table = None
+        elif self.objects is not None:
+            raise ValueError("scene: objects need kind 'file', got %r" % self.kind)
+
+    @classmethod
+    def from_config(cls, cfg, source_frequency: float = 1.0) -> "Scene":
+        """The scene of a ``SchemeConfig``: the one constructor of the scheme,
+        its capacity plan and the driver."""
+        objects, smoothing = None, "linear"
+        if cfg.scene == "file":
+            if cfg.scene_objects is not None:
+                objects, smoothing = cfg.scene_objects, cfg.scene_smoothing
+            elif cfg.scene_file:
+                objects, smoothing = load_scene_file(cfg.scene_file)
+            else:
+                raise ValueError("scene: kind 'file' needs objects or a scene file")
+        return cls(cfg.scene, cfg.scheme, source_frequency, cfg.sphere_eps, cfg.sphere_radius,
+                   tuple(cfg.sphere_center), objects, smoothing)
+
+    def table(self):
+        """The objects as the table of ``ops.scene_sample`` (kind "file")."""
+        if self._table is None:
+            self._table = build_table(self.objects, self.scheme, self.smoothing, self.source_frequency)
+        return self._table
 
     # ------------------------------------------------------------------
     def _coords(self, lo: Sequence[int], shape: Sequence[int], mod: float, device, dtype):
@@ -57,6 +94,8 @@ class Scene:
         return x, y, z
 
     def is_vacuum(self, metamaterials: bool) -> bool:
+        if self.kind == "file":
+            return self.uniform("eps") == 1.0 and (not metamaterials or self.uniform("omega_pe") == 0.0)
         if self.kind == "vacuum" or (self.kind == "drude-sphere" and not metamaterials):
             return True
         if self.kind == "reference" and self.scheme != "3d" and not metamaterials:
@@ -89,6 +128,10 @@ class Scene:
         of evaluating and averaging a full fp64 grid (8 GB per array at
         1024^3)."""
         two_d_ref = self.kind == "reference" and self.scheme != "3d"
+        if self.kind == "file" and name == "eps":
+            return None if any(o.eps != 1.0 for o in self.objects) else 1.0
+        if self.kind == "file" and name == "omega_pe":
+            return None if any(o.omega_p != 0.0 for o in self.objects) else 0.0
         if name == "eps":
             return 1.0 if self.kind in ("vacuum", "drude-sphere") or two_d_ref else None
         if name == "mu":
@@ -139,7 +182,7 @@ class MaterialSampler:
     averages it onto field components."""
 
     def __init__(self, layout: YeeLayout, scene: Scene, origin: Sequence[int], shape: Sequence[int],
-                 device, dtype=torch.float64):
+                 device, dtype=torch.float64, ops=None):
         self.layout = layout
         self.scene = scene
         self.origin = tuple(origin)
@@ -149,6 +192,8 @@ class MaterialSampler:
         self.double = layout.double_material_precision
         self.mod = 2.0 if self.double else 1.0
         self._cache: Dict[str, torch.Tensor] = {}
+        # file scenes: the backend whose scene_sample op evaluates them (the torch oracle when none is given)
+        self.ops = ops
 
     def _eps_region(self):
         if self.double:
@@ -163,6 +208,12 @@ class MaterialSampler:
         return lo, shp
 
     def grid(self, name: str) -> torch.Tensor:
+        if name not in self._cache and self.scene.kind == "file":
+            lo, shp = self._eps_region()
+            if name in ("eps", "omega_pe"):
+                self._cache[name] = self._sample(name, [(0, 0, 0)], lo, shp, (1, 1, 1))
+            else:
+                self._cache[name] = torch.full(shp, 1.0 if name == "mu" else 0.0, dtype=self.dtype, device=self.device)
         if name not in self._cache:
             lo, shp = self._eps_region()
             x, y, z = self.scene._coords(lo, shp, self.mod, self.device, self.dtype)
@@ -189,12 +240,46 @@ class MaterialSampler:
         # drop duplicate points created by inactive axes (keeps 2D/1D averages exact)
         return _dedupe_points(comp, pts, act, self.double)
 
+    def _sample(self, name: str, points, origin, shape, stride) -> torch.Tensor:
+        """A file scene's ``name`` (eps / omega_pe) through the backend op."""
+        if self.ops is None:
+            from ..ops.torch_ops import TorchOps
+            self.ops = TorchOps(self.layout, self.device, self.dtype)
+        return self.ops.scene_sample(self.scene.table(), "eps" if name == "eps" else "omega", points, origin, shape,
+                                     stride, self.mod)
+
+    def _stencil(self, comp: str):
+        """(points, origin, stride) of component ``comp`` for ``scene_sample``:
+        the eps-grid offsets :meth:`_points` slices at, an inactive axis at its
+        single plane."""
+        act = [self.layout.active(d) for d in range(3)]
+        if not self.double:
+            pts = [tuple(off[d] if act[d] else 0 for d in range(3)) for off in MATERIAL_STENCIL[comp]]
+        else:
+            pts = [tuple((2 * base[d] + sub[d]) if act[d] else 0 for d in range(3))
+                   for base, sub in MATERIAL_STENCIL_DOUBLE[comp]]
+        pts = _dedupe_points(comp, pts, act, self.double)
+        origin = tuple(self.origin[d] if act[d] else 0 for d in range(3))
+        stride = tuple(2 if (self.double and act[d]) else 1 for d in range(3))
+        return pts, origin, stride
+
     def averaged(self, comp: str, name: str) -> torch.Tensor:
         """Material ``name`` averaged at the positions of component ``comp``
         over the local allocated region (shape == local field shape)."""
+        if self.scene.kind == "file":
+            if name != "eps":
+                return torch.full(self.shape, 1.0 if name == "mu" else 0.0, dtype=self.dtype, device=self.device)
+            pts, origin, stride = self._stencil(comp)
+            return self._sample("eps", pts, origin, self.shape, stride)
         return approximate_material(self._points(comp, self.grid(name)))
 
     def averaged_drude(self, comp: str, electric: bool):
+        if self.scene.kind == "file":
+            # (gamma = 0 in every file scene: the scalar the callers' expressions take)
+            if not electric:
+                return torch.zeros(self.shape, dtype=self.dtype, device=self.device), 0.0
+            pts, origin, stride = self._stencil(comp)
+            return self._sample("omega_pe", pts, origin, self.shape, stride), 0.0
         w = self._points(comp, self.grid("omega_pe" if electric else "omega_pm"))
         g = self._points(comp, self.grid("gamma_e" if electric else "gamma_m"))
         return approximate_drude(w, g)

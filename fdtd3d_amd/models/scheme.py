@@ -95,6 +95,9 @@ class SchemeConfig:
     sphere_eps: float = 2.0
     sphere_radius: float = 20.0
     sphere_center: Tuple[float, float, float] = (40.5, 40.5, 40.5)
+    scene_file: str = ""                     # scene "file": the JSON scene file (layout/scene_file.py)
+    scene_objects: Optional[Sequence] = None  # scene "file" from Python: the objects, instead of a file
+    scene_smoothing: str = "linear"          # with scene_objects: linear | none
     source: str = "sine"                     # sine | gaussian
     gaussian_width: float = 30.0
     gaussian_delay: float = 120.0
@@ -157,6 +160,17 @@ class SchemeConfig:
         else:
             scheme = "1d"
             size = (s.sizeX, 1, 1)
+        scene_objects, scene_smoothing = None, "linear"
+        if s.scene == "file":
+            # read once, here: everything the format or the scheme refuses is a SettingsError
+            # before anything is set up
+            from ..layout.scene_file import check_scheme, load_scene_file
+            from ..utils.settings import SettingsError
+            scene_objects, scene_smoothing = load_scene_file(s.sceneFile)
+            try:
+                check_scheme(scene_objects, scheme)
+            except ValueError as e:
+                raise SettingsError("--scene-file %s: %s" % (s.sceneFile, e))
         return cls(
             scheme=scheme, size=size, time_steps=s.numTimeSteps, amplitude_steps=s.numAmplitudeTimeSteps,
             pml_size=(s.pmlSizeX, s.pmlSizeY, s.pmlSizeZ), tfsf_size=(s.tfsfSizeX, s.tfsfSizeY, s.tfsfSizeZ),
@@ -168,6 +182,7 @@ class SchemeConfig:
             wavelength=s.sourceWaveLength, courant=s.courantNum, dtype=s.valueType,
             complex_values=s.doUseComplexFieldValues, scene=s.scene, sphere_eps=s.sphereEps,
             sphere_radius=s.sphereRadius, sphere_center=(s.sphereCenterX, s.sphereCenterY, s.sphereCenterZ),
+            scene_file=s.sceneFile, scene_objects=scene_objects, scene_smoothing=scene_smoothing,
             source=s.sourceType, gaussian_width=s.gaussianWidth, gaussian_delay=s.gaussianDelay,
             ntff_step=s.ntffStep, check_finite=s.doCheckFinite, finite_check_step=s.finiteCheckStep,
             use_fused=not s.doUseSplitKernels, cpml_kappa_max=s.cpmlKappaMax, cpml_alpha_max=s.cpmlAlphaMax,
@@ -311,11 +326,10 @@ class YeeScheme(BlockedStepping):
         self._check_capacity(self.mem_plan)
         self.F: List[Dict[str, torch.Tensor]] = [{c: self._zeros() for c in self.comps} for _ in range(self.planes)]
 
-        self.scene = Scene(cfg.scene, cfg.scheme, self.source_frequency, cfg.sphere_eps, cfg.sphere_radius,
-                           tuple(cfg.sphere_center))
+        self.scene = Scene.from_config(cfg, self.source_frequency)
         vacuum = self.scene.is_vacuum(cfg.use_metamaterials)
         self.vacuum = vacuum
-        sampler = MaterialSampler(self.layout, self.scene, dom.origin, shape, self.device)
+        sampler = MaterialSampler(self.layout, self.scene, dom.origin, shape, self.device, ops=self.ops)
         self.sampler = sampler
         dt, dx = self.dt, self.dx
 
@@ -478,7 +492,7 @@ class YeeScheme(BlockedStepping):
         isz = 4 if cfg.dtype == "f32" else 8
         planes = self.planes
         plan = {"fields": 6 * isz * cells * planes}
-        scene = Scene(cfg.scene, cfg.scheme)
+        scene = Scene.from_config(cfg)
         blocked = cfg.use_fused and cfg.scheme in ("3d", "tmz", "tez") and self.ops.name == "hip"
         if blocked or cfg.use_tfsf:
             plan["fields_pingpong"] = plan["fields"]
@@ -525,6 +539,10 @@ class YeeScheme(BlockedStepping):
             slab = sum(2 * pml[a] * (cells // max(1, n[a])) for a in range(3) if self.layout.active(a))
             plan["cpml_psi"] = 2 * 4 * isz * slab * planes  # ~4 terms per slab cell, two copies
         plan["init_transient"] = 4 * 8 * cells if not scene.is_vacuum(cfg.use_metamaterials) else 0
+        if cfg.scene == "file" and plan["init_transient"]:
+            # no eps-layout grid: scene_sample writes the averaged fp64 material of a component directly;
+            # the three E components' arrays live until their coefficients are built
+            plan["init_transient"] = 3 * 8 * cells if scene.uniform("eps") is None else 8 * cells
         return plan
 
     def _check_capacity(self, plan: Dict[str, int]) -> None:
@@ -755,7 +773,7 @@ class YeeScheme(BlockedStepping):
             for x0 in range(0, shape[0], xc):
                 n = min(xc, shape[0] - x0)
                 smp = MaterialSampler(self.layout, self.scene, (dom.origin[0] + x0, dom.origin[1], dom.origin[2]),
-                                      (n, shape[1], shape[2]), self.device)
+                                      (n, shape[1], shape[2]), self.device, ops=self.ops)
                 w, _ = smp.averaged_drude(c, electric)
                 yield x0, n, w
                 del smp, w

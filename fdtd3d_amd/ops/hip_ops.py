@@ -29,6 +29,7 @@ from ..models.regions import RegionLevel
 from .coef import Coef
 from .hip_lib import HipError, _check, _ptr, _stream, c_double, c_int, c_ll, c_vp
 from .hip_monitors import HipMonitorOps
+from .hip_scene import HipSceneOps
 
 Box = Tuple[Tuple[int, int, int], Tuple[int, int, int]]
 
@@ -139,7 +140,7 @@ class _LibProxy:
 _EMPTY_CPML = ((c_vp * 45)(), (c_int * 36)())
 
 
-class HipOps(HipMonitorOps):
+class HipOps(HipMonitorOps, HipSceneOps):
     name = "hip"
     # fp64 3D split updates on the double4 lanes of yee3d_cpml.hip (FDTD3D_F64_V4=1): 512^3 stepped vacuum
     # +6%, but the UPML shell windows -3% (profiles/physics_r6.md): off by default

@@ -1,0 +1,67 @@
+"""The ``scene_sample`` operation of the HIP backend, a mixin of
+:class:`~.hip_ops.HipOps` (csrc/scene_kernels.hip): a file scene's objects
+evaluated at a component's material stencil and averaged, in one launch.
+Everything is validated before the launch; a missing kernel is an error.
+"""
+
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from ..layout.scene_file import SCENE_ENT_SIZE, SCENE_MAX_OBJECTS, SceneTable, sample_args
+from .hip_lib import HipError, _check, _ptr, _stream, c_double, c_int
+
+
+class HipSceneOps:
+    """Needs ``lib``, ``device`` and ``launches`` of :class:`~.hip_ops.HipOps`."""
+
+    def _scene_table(self, table: SceneTable) -> torch.Tensor:
+        """The table on the device (at least one entry, so never a null
+        pointer), cached on ``table`` per device."""
+        raw = self.lib.raw
+        if int(raw.fdtd_scene_ent_size()) != SCENE_ENT_SIZE or int(raw.fdtd_scene_max_objects()) != SCENE_MAX_OBJECTS:
+            raise HipError("SceneEnt layout mismatch")
+        key = str(torch.device(self.device))
+        dev = table.device_tables.get(key)
+        if dev is None:
+            host = torch.zeros((max(1, len(table)), SCENE_ENT_SIZE), dtype=torch.uint8)
+            if len(table):
+                host[:len(table)] = torch.from_numpy(table.ents.view("u1").reshape(len(table), SCENE_ENT_SIZE).copy())
+            dev = table.device_tables[key] = host.to(self.device)
+        return dev
+
+    def scene_sample(self, table, quantity: str, points, origin, shape, stride, mod, out=None,
+                     cull: bool = True) -> torch.Tensor:
+        """The contract of ``TorchOps.scene_sample`` in ONE launch of
+        k_scene_sample.  ``out``: a contiguous fp64 device tensor of ``shape``
+        to fill (allocated otherwise); ``cull`` = False evaluates every object
+        at every cell (measurements)."""
+        if not isinstance(table, SceneTable):
+            raise HipError("scene_sample: a SceneTable, got %r" % type(table).__name__)
+        if len(table) > SCENE_MAX_OBJECTS:
+            raise HipError("scene_sample: %d objects, the table holds %d" % (len(table), SCENE_MAX_OBJECTS))
+        try:
+            q, pts, origin, shape, stride, mod = sample_args(quantity, points, origin, shape, stride, mod)
+        except ValueError as e:
+            raise HipError(str(e))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float64
+              or not out.is_contiguous() or tuple(out.shape) != shape):
+            raise HipError("scene_sample: out must be a contiguous float64 device tensor of shape %s" % (shape,))
+        if out.numel() == 0:
+            return out
+        if out.data_ptr() % 8:
+            raise HipError("scene_sample: out not aligned to its element size")
+        tab = self._scene_table(table)
+        i3 = ctypes.c_int * 3
+        flat = [v for p in pts for v in p]
+        f = self.lib.raw.fdtd_scene_sample
+        f.restype = c_int
+        rc = f(_ptr(tab), c_int(len(table)), c_int(q), (ctypes.c_int * len(flat))(*flat), c_int(len(pts)),
+               i3(*origin), i3(*shape), i3(*stride), c_double(mod), c_int(1 if cull else 0), _ptr(out), _stream())
+        _check(rc, "scene_sample")
+        self.launches += 1
+        return out

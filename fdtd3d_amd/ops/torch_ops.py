@@ -686,6 +686,84 @@ class TorchOps:
                 raise ValueError("probe_sample: contiguous field arrays")
             series[int(row), cols] = f.reshape(-1)[offs].double()
 
+    def scene_sample(self, table, quantity: str, points, origin, shape, stride, mod, out=None) -> torch.Tensor:
+        """A file scene (layout/scene_file.py ``SceneTable``) evaluated and
+        averaged onto one component: fp64 tensor of ``shape``.  Cell ``i`` takes
+        the points at eps-grid index ``stride * (origin + i) + offset`` (centre
+        ``+ 0.5``) for every offset of ``points``; at each the objects are
+        painted first to last over vacuum, then the points reduce as
+        ``approximate_material`` (eps) or ``approximate_drude`` (omega) do.
+        Every operation is rounded on its own, in the order the kernel of
+        csrc/scene_kernels.hip keeps, the square roots correctly (``_sqrt_rn``):
+        this is its oracle."""
+        from ..layout.approximation import approximate_material
+        from ..layout.scene_file import (FLAG_IGNORE_SHIFT, FLAG_SHARP, KIND_BOX, KIND_SPHERE, SceneTable,
+                                         sample_args)
+        if not isinstance(table, SceneTable):
+            raise ValueError("scene_sample: a SceneTable, got %r" % type(table).__name__)
+        q, pts, origin, shape, stride, mod = sample_args(quantity, points, origin, shape, stride, mod)
+        dev = self.device if out is None else out.device
+        if out is not None and (out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError("scene_sample: out must be contiguous float64 of shape %s" % (shape,))
+        vals = []
+        for off in pts:
+            ax = [(torch.arange(shape[d], dtype=torch.int64, device=dev) * stride[d]
+                   + (stride[d] * origin[d] + off[d])).to(torch.float64) + 0.5 for d in range(3)]
+            P = torch.meshgrid(ax[0], ax[1], ax[2], indexing="ij")
+            val = torch.full(shape, 1.0 if q == 0 else 0.0, dtype=torch.float64, device=dev)
+            for e in table.ents:
+                flags = int(e["flags"])
+                skip = [bool((flags >> (FLAG_IGNORE_SHIFT + a)) & 1) for a in range(3)]
+                a0 = [float(v) * mod for v in e["p"]]
+                b0 = [float(v) * mod for v in e["q"]]
+                if e["kind"] == KIND_BOX:
+                    d = None
+                    for a in range(3):
+                        if skip[a]:
+                            continue
+                        t = torch.maximum(a0[a] - P[a], P[a] - b0[a])
+                        d = t if d is None else torch.maximum(d, t)
+                elif e["kind"] == KIND_SPHERE:
+                    sq = [torch.zeros_like(P[a]) if skip[a] else (P[a] - a0[a]) * (P[a] - a0[a]) for a in range(3)]
+                    d = _sqrt_rn((sq[0] + sq[1]) + sq[2]) - b0[0]
+                else:
+                    ax_c = flags & 3
+                    b_, c_ = [a for a in range(3) if a != ax_c]
+                    db, dc = P[b_] - a0[b_], P[c_] - a0[c_]
+                    d = _sqrt_rn(db * db + dc * dc) - b0[0]
+                    if not skip[ax_c]:
+                        d = torch.maximum(d, torch.maximum(a0[ax_c] - P[ax_c], P[ax_c] - b0[1]))
+                if q == 1:
+                    val = torch.where(d < 0, torch.full_like(val, float(e["omega"])), val)
+                elif flags & FLAG_SHARP:
+                    val = torch.where(d < 0, torch.full_like(val, float(e["eps"])), val)
+                else:
+                    eps_in = float(e["eps"])
+                    prop = 0.5 - d
+                    mid = prop * eps_in + (1 - prop) * val
+                    o = torch.where(d < -0.5, torch.full_like(val, eps_in), mid)
+                    val = torch.where(d > 0.5, val, o)
+            vals.append(val)
+        if q == 0:
+            res = approximate_material(vals)
+        else:
+            res = _sqrt_rn(sum(w * w for w in vals) / float(len(vals)))
+        if out is None:
+            return res.contiguous()
+        out.copy_(res)
+        return out
+
+
+def _sqrt_rn(t: torch.Tensor) -> torch.Tensor:
+    """The correctly rounded fp64 square root.  ``torch.sqrt`` on the CPU is
+    not: about 0.7% of arguments come out one ulp off (for instance
+    sqrt(19.637599999999992)); numpy's is the hardware instruction.  On a
+    device ``torch.sqrt`` is the device library's correctly rounded one."""
+    if t.device.type != "cpu":
+        return torch.sqrt(t)
+    import numpy as np
+    return torch.from_numpy(np.sqrt(t.contiguous().numpy()))
+
 
 class TfsfTable:
     """Per-component TF/SF correction list: ``target[off] += coef *

@@ -100,7 +100,7 @@ def build(settings: Settings, rank: int = 0, world: int = 1):
         if tb <= 0:  # automatic: the scheme's own rule (models/blocking.py auto_time_block)
             from .layout.materials import Scene
             from .models.blocking import auto_time_block
-            percell = Scene(cfg.scene, cfg.scheme).percell_kinds(cfg.use_metamaterials)
+            percell = Scene.from_config(cfg).percell_kinds(cfg.use_metamaterials)
             tb = auto_time_block(cfg.scheme, cfg.dtype, backend, percell, world) if plain else 1
         if tb > 1 and cfg.scheme in ("3d", "tmz", "tez"):
             buf = tb  # blocked passes exchange tb-deep ghosts every tb steps
@@ -177,6 +177,15 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                or refuse_probe_config(cfg0, checkpoints=ckpt))
         if why:
             out.write("ERROR: %s\n" % why)
+            return EXIT_ERROR
+    if settings.scene == "file":
+        # the scene file is read and refused here, before anything is set up
+        from .models.scheme import SchemeConfig
+        from .utils.settings import SettingsError
+        try:
+            SchemeConfig.from_settings(settings)
+        except SettingsError as e:
+            out.write("ERROR: %s\n" % e)
             return EXIT_ERROR
     dist, rank, world = _init_distributed(settings)
     log.set_rank(rank)
@@ -395,6 +404,8 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                 rec["energy"] = energy.info(energy_result)
             if probes_info is not None:
                 rec["probes"] = probes_info
+            if scheme.cfg.scene == "file":
+                rec["scene"] = {"objects": len(scheme.scene.objects)}
             if breakdown is not None:
                 rec["rank0_passes"] = breakdown  # decomposed passes: interior / exchange wait / shell ms
             if scheme.device.type == "cuda":
