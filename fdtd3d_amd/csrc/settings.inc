@@ -121,7 +121,7 @@ FDTD_FLOAT (gaussianWidth, "--gaussian-width", 30.0, "Gaussian pulse width (step
 FDTD_FLOAT (gaussianDelay, "--gaussian-delay", 120.0, "Gaussian pulse delay (steps)")
 FDTD_FLOAT (courantNum, "--courant", 0.5, "Courant number c*dt/dx")
 FDTD_STRING (scene, "--scene", "reference", "Material scene: reference (hardcoded sphere setup), vacuum, sphere (dielectric) or drude-sphere (dispersive sphere in vacuum, needs --use-metamaterials); file (boxes, spheres and cylinders from --scene-file; Python driver)")
-FDTD_STRING (sceneFile, "--scene-file", "", "With --scene file: the JSON scene file -- box (lo, hi), sphere (center, radius) and cylinder (axis, center, radius, span) objects painted first to last over vacuum, each with eps and omega_p (in units of 2 pi f of the source; used with --use-metamaterials), coordinates in cells; smoothing linear or none")
+FDTD_STRING (sceneFile, "--scene-file", "", "With --scene file: the JSON scene file -- box (lo, hi), sphere (center, radius), cylinder (axis, center, radius, span) and mesh (file = a closed STL surface, or vertices + triangles; scale, translate; 3D) objects painted first to last over vacuum, each with eps and omega_p (in units of 2 pi f of the source; used with --use-metamaterials), coordinates in cells; smoothing linear or none")
 FDTD_FLOAT (sphereEps, "--sphere-eps", 2.0, "Relative permittivity of the dielectric sphere")
 FDTD_FLOAT (sphereRadius, "--sphere-radius", 20.0, "Radius (cells) of the dielectric sphere")
 FDTD_FLOAT (sphereCenterX, "--sphere-center-x", 40.5, "Sphere centre x (cells)")

@@ -1,4 +1,5 @@
-"""Scene files: user-defined boxes, spheres and cylinders (``--scene file``).
+"""Scene files: user-defined boxes, spheres, cylinders and closed triangle
+meshes (``--scene file``).
 
 A scene is a list of objects painted over vacuum, first to last (painter's
 order).  JSON, standard library only::
@@ -7,7 +8,8 @@ order).  JSON, standard library only::
      "objects": [
       {"shape": "box",      "lo": [0, 0, 0], "hi": [64, 64, 20], "eps": 2.25},
       {"shape": "sphere",   "center": [32.5, 32.5, 30.5], "radius": 8, "eps": 1.0, "omega_p": 1.4142135},
-      {"shape": "cylinder", "axis": "z", "center": [20.5, 40.5], "radius": 3, "span": [20, 50], "eps": 4.0}
+      {"shape": "cylinder", "axis": "z", "center": [20.5, 40.5], "radius": 3, "span": [20, 50], "eps": 4.0},
+      {"shape": "mesh",     "file": "target.stl", "scale": 0.25, "translate": [32.5, 32.5, 30.0], "eps": 2.56}
      ]}
 
 Coordinates are in cells on the eps layout (cell centre ``m + 0.5``, the
@@ -22,6 +24,16 @@ largest of ``lo_a - p_a``, ``p_a - hi_a`` over the axes -- exact on faces, a
 Chebyshev distance at edges and corners (the smoothed zone there is square,
 not rounded); cylinder the larger of the radial and the axial distance.
 
+A mesh is a closed, consistently oriented triangle surface, inline
+(``vertices`` + ``triangles``) or from a binary or ASCII STL ``file`` (resolved
+against the scene file's directory, from Python against the working
+directory); a vertex sits at ``scale * v + translate`` (fp64, once, here).  It
+is not rotated.  Its ``d`` is negative where a ray along +z crosses the surface
+an odd number of times (the even-odd rule; a ray through a projected edge or
+vertex counts as the same ray displaced by an infinitesimal (-e^2, +e) would),
+and its magnitude is the Euclidean distance to the closest triangle.  A point
+exactly on the surface may fall on either side.  3D schemes only.
+
 This module also defines the fixed-size table entry both backends'
 ``scene_sample`` op reads (csrc/scene_kernels.hip ``SceneEnt``).
 """
@@ -30,6 +42,8 @@ from __future__ import annotations
 
 import json
 import math
+import os
+import struct
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -41,25 +55,52 @@ SCENE_ENT = np.dtype([("kind", "<i4"), ("flags", "<i4"), ("p", "<f8", (3,)), ("q
 SCENE_ENT_SIZE = 72      # bytes of a table entry (fdtd_scene_ent_size)
 assert SCENE_ENT.itemsize == SCENE_ENT_SIZE
 
-KIND_BOX, KIND_SPHERE, KIND_CYLINDER = 0, 1, 2
+SCENE_MAX_TRIANGLES = 2 ** 20  # over all meshes of a scene (fdtd_scene_max_triangles)
+
+KIND_BOX, KIND_SPHERE, KIND_CYLINDER, KIND_MESH = 0, 1, 2, 3
 # SceneEnt.flags: bits 0-1 the cylinder's axis, bits 2-4 the axes the object
 # ignores (the inactive axis of a 2D scheme), bit 5 sharp eps (smoothing none)
 FLAG_IGNORE_SHIFT = 2
 FLAG_SHARP = 32
 
-SHAPES = ("box", "sphere", "cylinder")
+SHAPES = ("box", "sphere", "cylinder", "mesh")
 SMOOTHINGS = ("linear", "none")
 _KEYS = {"box": {"shape", "lo", "hi", "eps", "omega_p"},
          "sphere": {"shape", "center", "radius", "eps", "omega_p"},
-         "cylinder": {"shape", "axis", "center", "radius", "span", "eps", "omega_p"}}
+         "cylinder": {"shape", "axis", "center", "radius", "span", "eps", "omega_p"},
+         "mesh": {"shape", "file", "vertices", "triangles", "scale", "translate", "eps", "omega_p"}}
 _AXES = {"x": 0, "y": 1, "z": 2}
+
+
+class Mesh:
+    """The triangles of a validated mesh: ``tris`` = (n, 3, 3) fp64, vertex
+    coordinates in cells (scaled and translated), the three vertices of every
+    triangle in ascending (x, y, z) order -- the one order both backends
+    evaluate a triangle and its edges in, whichever way the input wound it."""
+    __slots__ = ("tris",)
+
+    def __init__(self, tris: np.ndarray):
+        self.tris = tris
+
+    def __len__(self) -> int:
+        return len(self.tris)
+
+    def __eq__(self, other):
+        return isinstance(other, Mesh) and np.array_equal(self.tris, other.tris)
+
+    def __hash__(self):
+        return hash(self.tris.shape)
+
+    def __repr__(self):
+        return "Mesh(%d triangles)" % len(self.tris)
 
 
 @dataclass(frozen=True)
 class SceneObject:
     """One validated object.  Box: ``a`` = lo, ``b`` = hi.  Sphere: ``a`` =
     centre, ``radius``.  Cylinder: ``axis``, ``a`` = centre with the span's
-    lower end at ``axis``, ``b[axis]`` = the span's upper end, ``radius``."""
+    lower end at ``axis``, ``b[axis]`` = the span's upper end, ``radius``.
+    Mesh: ``mesh``, ``a`` / ``b`` = the lower / upper corner of its bounding box."""
     shape: str
     a: Tuple[float, float, float]
     b: Tuple[float, float, float] = (0.0, 0.0, 0.0)
@@ -67,6 +108,7 @@ class SceneObject:
     axis: int = 0
     eps: float = 1.0
     omega_p: float = 0.0
+    mesh: Optional[Mesh] = None
 
 
 def _number(v, what: str) -> float:
@@ -84,21 +126,154 @@ def _vector(v, n: int, what: str) -> Tuple[float, ...]:
     return tuple(_number(x, what) for x in v)
 
 
-def parse_object(o, index: int = 0) -> SceneObject:
+_STL_RECORD = np.dtype([("normal", "<f4", (3,)), ("v", "<f4", (3, 3)), ("attr", "<u2")])
+assert _STL_RECORD.itemsize == 50
+
+
+def _too_many_triangles(n: int) -> ValueError:
+    return ValueError("scene: %d triangles, a scene holds %d" % (n, SCENE_MAX_TRIANGLES))
+
+
+def load_stl(path: str) -> np.ndarray:
+    """The triangles of the STL file ``path`` as stored: (n, 3, 3) fp64.  The
+    file is binary when its size is 84 + 50 * the count after its 80-byte
+    header, otherwise ASCII (solid / facet normal / vertex); stored normals
+    are ignored.  ValueError for a file that is neither."""
+    try:
+        size = os.path.getsize(path)
+        with open(path, "rb") as f:
+            head = f.read(84)
+            if len(head) == 84:
+                count = struct.unpack("<I", head[80:])[0]
+                if size == 84 + 50 * count:
+                    if count > SCENE_MAX_TRIANGLES:
+                        raise _too_many_triangles(count)
+                    rec = np.fromfile(f, dtype=_STL_RECORD, count=count)
+                    if len(rec) == count:
+                        return rec["v"].astype(np.float64)
+            f.seek(0)
+            data = f.read()
+    except OSError as e:
+        raise ValueError("scene: STL file %s: %s" % (path, e.strerror or e))
+    bad = ValueError("scene: STL file %s is neither a binary STL of the size its header states (truncated?) "
+                     "nor a complete ASCII STL" % path)
+    try:
+        lines = data.decode("ascii").splitlines()
+    except UnicodeDecodeError:
+        raise bad
+    if not lines or lines[0].split()[:1] != ["solid"]:
+        raise bad
+    corners, in_loop, ended = [], None, False
+    for line in lines[1:]:
+        w = line.split()
+        if not w:
+            continue
+        if w[0] == "vertex" and len(w) == 4 and in_loop is not None:
+            try:
+                corners.append((float(w[1]), float(w[2]), float(w[3])))
+            except ValueError:
+                raise bad
+            in_loop += 1
+        elif w[0] == "outer" and in_loop is None:
+            in_loop = 0
+            if len(corners) >= 3 * SCENE_MAX_TRIANGLES:
+                raise _too_many_triangles(len(corners) // 3 + 1)
+        elif w[0] == "endloop" and in_loop == 3:
+            in_loop = None
+        elif w[0] in ("facet", "endfacet") and in_loop is None:
+            pass
+        elif w[0] == "endsolid" and in_loop is None:
+            ended = True
+            break
+        else:
+            raise bad
+    if not ended:
+        raise bad
+    return np.asarray(corners, dtype=np.float64).reshape(-1, 3, 3)
+
+
+def _mesh(o: dict, what: str, base_dir: Optional[str]) -> Tuple[Mesh, Tuple[float, ...], Tuple[float, ...]]:
+    """(mesh, bounding box lo, hi) of a mesh object's dictionary: read, welded,
+    scaled and translated, then checked to be a closed, consistently oriented
+    surface of triangles with area."""
+    inline = [k in o for k in ("vertices", "triangles")]
+    if ("file" in o) == any(inline) or (any(inline) and not all(inline)):
+        raise ValueError("scene: %sneeds either 'file' or both 'vertices' and 'triangles'" % what)
+    scale = _number(o.get("scale", 1.0), what + "scale")
+    if scale <= 0:
+        raise ValueError("scene: %sscale must be positive, got %r" % (what, scale))
+    translate = _vector(o.get("translate", (0.0, 0.0, 0.0)), 3, what + "translate")
+    if "file" in o:
+        if not isinstance(o["file"], str) or not o["file"]:
+            raise ValueError("scene: %sfile must be a path, got %r" % (what, o["file"]))
+        corners = load_stl(o["file"] if base_dir is None else os.path.join(base_dir, o["file"]))
+        # weld: corners whose three values are exactly equal are one vertex
+        verts, tri = np.unique(corners.reshape(-1, 3), axis=0, return_inverse=True)
+        tri = tri.reshape(-1, 3)
+    else:
+        if not isinstance(o["triangles"], (list, tuple)) or not isinstance(o["vertices"], (list, tuple)):
+            raise ValueError("scene: %svertices and triangles must be lists" % what)
+        if len(o["triangles"]) > SCENE_MAX_TRIANGLES:
+            raise _too_many_triangles(len(o["triangles"]))
+        try:
+            verts, tri = np.asarray(o["vertices"]), np.asarray(o["triangles"])
+        except ValueError:   # ragged lists
+            verts = tri = np.empty((0,), dtype=object)
+        if len(o["vertices"]) and (verts.ndim != 2 or verts.shape[1] != 3 or verts.dtype.kind not in "iuf"):
+            raise ValueError("scene: %svertices must be lists of 3 numbers" % what)
+        if len(o["triangles"]) and (tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu"):
+            raise ValueError("scene: %striangles must be lists of 3 vertex indices" % what)
+        verts, tri = verts.astype(np.float64).reshape(-1, 3), tri.astype(np.int64).reshape(-1, 3)
+    if not np.isfinite(verts).all():
+        raise ValueError("scene: %svertices must be finite" % what)
+    if len(tri) < 4:
+        raise ValueError("scene: %shas %d triangles: a closed mesh has at least 4" % (what, len(tri)))
+    if int(tri.min()) < 0 or int(tri.max()) >= len(verts):
+        raise ValueError("scene: %shas a vertex index out of range (%d vertices)" % (what, len(verts)))
+    p = scale * verts + np.asarray(translate, dtype=np.float64)
+    if not np.isfinite(p).all():
+        raise ValueError("scene: %svertices must be finite after scale and translate" % what)
+    i, j, k = tri[:, 0], tri[:, 1], tri[:, 2]
+    rep = np.flatnonzero((i == j) | (j == k) | (k == i))
+    if len(rep):
+        raise ValueError("scene: %striangle %d repeats a vertex" % (what, rep[0]))
+    flat = np.flatnonzero(~np.cross(p[j] - p[i], p[k] - p[i]).any(axis=1))
+    if len(flat):
+        raise ValueError("scene: %striangle %d is degenerate (its cross product is zero)" % (what, flat[0]))
+    # every undirected edge in exactly two triangles, once in each direction
+    u, v = np.concatenate((i, j, k)), np.concatenate((j, k, i))
+    nv = len(verts)
+    und, counts = np.unique(np.minimum(u, v) * nv + np.maximum(u, v), return_counts=True)
+    if (counts != 2).any():
+        e = int(und[np.flatnonzero(counts != 2)[0]])
+        raise ValueError("scene: %sis not closed: the edge between vertices %d and %d belongs to %d triangles, "
+                         "not 2" % (what, e // nv, e % nv, int(counts[counts != 2][0])))
+    if len(np.unique(u * nv + v)) != len(u):
+        raise ValueError("scene: %sis not consistently oriented: two triangles run along an edge in the same "
+                         "direction" % what)
+    t = p[tri]
+    order = np.lexsort((t[:, :, 2], t[:, :, 1], t[:, :, 0]), axis=1)
+    t = np.ascontiguousarray(np.take_along_axis(t, order[:, :, None], axis=1))
+    lo, hi = t.reshape(-1, 3).min(axis=0), t.reshape(-1, 3).max(axis=0)
+    return Mesh(t), tuple(float(x) for x in lo), tuple(float(x) for x in hi)
+
+
+def parse_object(o, index: int = 0, base_dir: Optional[str] = None) -> SceneObject:
     """A :class:`SceneObject` from its JSON dictionary; ValueError with a
-    message for everything the format refuses."""
+    message for everything the format refuses.  ``base_dir``: the directory a
+    mesh's ``file`` is resolved against (None: the working directory)."""
     if isinstance(o, SceneObject):
         return o
     if not isinstance(o, dict):
         raise ValueError("scene: object %d must be a dictionary, got %r" % (index, o))
     shape = o.get("shape")
     if shape not in SHAPES:
-        raise ValueError("scene: object %d has unknown shape %r (box, sphere or cylinder)" % (index, shape))
+        raise ValueError("scene: object %d has unknown shape %r (box, sphere, cylinder or mesh)" % (index, shape))
     unknown = sorted(set(o) - _KEYS[shape])
     if unknown:
         raise ValueError("scene: object %d (%s) has unknown key %r" % (index, shape, unknown[0]))
     what = "object %d (%s) " % (index, shape)
-    for k in sorted(_KEYS[shape] - {"eps", "omega_p"} - set(o)):
+    for k in sorted(_KEYS[shape] - {"eps", "omega_p"} - set(o) if shape != "mesh" else ()):
         raise ValueError("scene: %sneeds %r" % (what, k))
     eps = _number(o.get("eps", 1.0), what + "eps")
     omega_p = _number(o.get("omega_p", 0.0), what + "omega_p")
@@ -106,6 +281,9 @@ def parse_object(o, index: int = 0) -> SceneObject:
         raise ValueError("scene: %seps must be positive, got %r" % (what, eps))
     if omega_p < 0:
         raise ValueError("scene: %somega_p must not be negative, got %r" % (what, omega_p))
+    if shape == "mesh":
+        mesh, lo, hi = _mesh(o, what, base_dir)
+        return SceneObject("mesh", lo, hi, eps=eps, omega_p=omega_p, mesh=mesh)
     if shape == "box":
         lo, hi = _vector(o["lo"], 3, what + "lo"), _vector(o["hi"], 3, what + "hi")
         if any(l >= h for l, h in zip(lo, hi)):
@@ -128,29 +306,39 @@ def parse_object(o, index: int = 0) -> SceneObject:
     return SceneObject("cylinder", tuple(a), tuple(b), radius=radius, axis=axis, eps=eps, omega_p=omega_p)
 
 
-def parse_objects(objects: Sequence, smoothing: str = "linear") -> Tuple[SceneObject, ...]:
+def parse_objects(objects: Sequence, smoothing: str = "linear",
+                  base_dir: Optional[str] = None) -> Tuple[SceneObject, ...]:
     if smoothing not in SMOOTHINGS:
         raise ValueError("scene: smoothing must be linear or none, got %r" % (smoothing,))
     if not isinstance(objects, (list, tuple)):
         raise ValueError("scene: objects must be a list, got %r" % (objects,))
     if len(objects) > SCENE_MAX_OBJECTS:
         raise ValueError("scene: %d objects, the table holds %d" % (len(objects), SCENE_MAX_OBJECTS))
-    return tuple(parse_object(o, n) for n, o in enumerate(objects))
+    out, triangles = [], 0
+    for n, o in enumerate(objects):
+        out.append(parse_object(o, n, base_dir))
+        triangles += len(out[-1].mesh) if out[-1].mesh is not None else 0
+        if triangles > SCENE_MAX_TRIANGLES:
+            raise _too_many_triangles(triangles)
+    return tuple(out)
 
 
 def check_scheme(objects: Sequence[SceneObject], scheme: str) -> None:
     """What a scheme refuses: every file scene in 1D, a cylinder that does
-    not lie along the inactive axis in 2D."""
+    not lie along the inactive axis in 2D, a mesh in 2D."""
     if scheme == "1d":
         raise ValueError("scene: file scenes need a 2D or 3D scheme")
     if scheme in ("tmz", "tez"):
         for n, o in enumerate(objects):
             if o.shape == "cylinder" and o.axis != 2:
                 raise ValueError("scene: object %d: a cylinder of a 2D scheme must lie along z, the inactive axis" % n)
+            if o.shape == "mesh":
+                raise ValueError("scene: object %d: a mesh needs a 3D scheme" % n)
 
 
-def parse_scene(doc) -> Tuple[Tuple[SceneObject, ...], str]:
-    """(objects, smoothing) of a parsed scene document."""
+def parse_scene(doc, base_dir: Optional[str] = None) -> Tuple[Tuple[SceneObject, ...], str]:
+    """(objects, smoothing) of a parsed scene document; ``base_dir`` as in
+    :func:`parse_object`."""
     if not isinstance(doc, dict):
         raise ValueError("scene: the file must hold one JSON object")
     unknown = sorted(set(doc) - {"smoothing", "objects"})
@@ -159,7 +347,7 @@ def parse_scene(doc) -> Tuple[Tuple[SceneObject, ...], str]:
     if "objects" not in doc:
         raise ValueError("scene: needs 'objects'")
     smoothing = doc.get("smoothing", "linear")
-    return parse_objects(doc["objects"], smoothing), smoothing
+    return parse_objects(doc["objects"], smoothing, base_dir), smoothing
 
 
 def load_scene_file(path: str) -> Tuple[Tuple[SceneObject, ...], str]:
@@ -173,7 +361,7 @@ def load_scene_file(path: str) -> Tuple[Tuple[SceneObject, ...], str]:
     try:
         with open(path, "r", encoding="utf-8") as f:
             doc = json.load(f, parse_constant=refuse_constant)
-        return parse_scene(doc)
+        return parse_scene(doc, os.path.dirname(os.path.abspath(path)))
     except OSError as e:
         raise SettingsError("--scene-file %s: %s" % (path, e.strerror or e))
     except ValueError as e:  # JSONDecodeError included
@@ -183,19 +371,45 @@ def load_scene_file(path: str) -> Tuple[Tuple[SceneObject, ...], str]:
 class SceneTable:
     """The objects as the table of ``ops.scene_sample``: ``ents`` = numpy
     records of :data:`SCENE_ENT`, coordinates in cells (the op scales them by
-    its ``mod``), ``omega`` = omega_p * 2 pi f in rad/s.  ``device_tables``
-    caches the HIP backend's copies, one per device."""
+    its ``mod``), ``omega`` = omega_p * 2 pi f in rad/s.  A mesh's entry holds
+    its bounding box in ``p`` / ``q``; its triangles are rows ``ranges[o, 0]``
+    to ``ranges[o, 0] + ranges[o, 1]`` of ``tris`` = (n, 3, 3) fp64 (vertices in
+    the order of :class:`Mesh`), ``ranges`` = (objects, 2) int32, zero for every
+    other kind.  ``device_tables`` caches the HIP backend's copies, one per
+    device."""
 
-    def __init__(self, ents: np.ndarray):
+    def __init__(self, ents: np.ndarray, tris: Optional[np.ndarray] = None, ranges: Optional[np.ndarray] = None):
         if ents.dtype != SCENE_ENT or ents.ndim != 1:
             raise ValueError("SceneTable: a 1D array of SCENE_ENT records")
         if len(ents) > SCENE_MAX_OBJECTS:
             raise ValueError("scene: %d objects, the table holds %d" % (len(ents), SCENE_MAX_OBJECTS))
+        tris = np.zeros((0, 3, 3), dtype=np.float64) if tris is None else tris
+        ranges = np.zeros((len(ents), 2), dtype=np.int32) if ranges is None else ranges
+        if tris.dtype != np.float64 or tris.ndim != 3 or tris.shape[1:] != (3, 3):
+            raise ValueError("SceneTable: tris of shape (n, 3, 3), float64")
+        if len(tris) > SCENE_MAX_TRIANGLES:
+            raise _too_many_triangles(len(tris))
+        if ranges.dtype != np.int32 or ranges.shape != (len(ents), 2):
+            raise ValueError("SceneTable: ranges of shape (objects, 2), int32")
         self.ents = ents
+        self.tris = tris
+        self.ranges = ranges
         self.device_tables = {}
 
     def __len__(self) -> int:
         return len(self.ents)
+
+    def has_meshes(self) -> bool:
+        return bool((self.ents["kind"] == KIND_MESH).any())
+
+    def range_error(self) -> Optional[str]:
+        """Why the triangle ranges do not fit ``tris`` (None: they do)."""
+        if self.ranges.shape != (len(self.ents), 2) or self.ranges.dtype != np.int32:
+            return "ranges of shape (objects, 2), int32"
+        r = self.ranges.astype(np.int64)
+        if len(r) and (int(r.min()) < 0 or int((r[:, 0] + r[:, 1]).max()) > len(self.tris)):
+            return "a triangle range past the %d triangles of the table" % len(self.tris)
+        return None
 
 
 def build_table(objects: Sequence[SceneObject], scheme: str = "3d", smoothing: str = "linear",
@@ -203,15 +417,21 @@ def build_table(objects: Sequence[SceneObject], scheme: str = "3d", smoothing: s
     objects = parse_objects(list(objects), smoothing)
     check_scheme(objects, scheme)
     ents = np.zeros(len(objects), dtype=SCENE_ENT)
+    ranges = np.zeros((len(objects), 2), dtype=np.int32)
+    tris, first = [], 0
     ignore = 0 if scheme == "3d" else 4  # 2D: objects ignore z
-    for e, o in zip(ents, objects):
+    for n, (e, o) in enumerate(zip(ents, objects)):
         e["kind"] = SHAPES.index(o.shape)
         e["flags"] = o.axis | (ignore << FLAG_IGNORE_SHIFT) | (FLAG_SHARP if smoothing == "none" else 0)
         e["p"] = o.a
-        e["q"] = o.b if o.shape == "box" else (o.radius, o.b[o.axis], 0.0)
+        e["q"] = o.b if o.shape in ("box", "mesh") else (o.radius, o.b[o.axis], 0.0)
         e["eps"] = o.eps
         e["omega"] = o.omega_p * 2 * math.pi * source_frequency
-    return SceneTable(ents)
+        if o.shape == "mesh":
+            ranges[n] = (first, len(o.mesh))
+            tris.append(o.mesh.tris)
+            first += len(o.mesh)
+    return SceneTable(ents, np.concatenate(tris) if tris else None, ranges)
 
 
 def sample_args(quantity: str, points, origin, shape, stride, mod):

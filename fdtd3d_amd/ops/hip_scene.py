@@ -1,6 +1,7 @@
 """The ``scene_sample`` operation of the HIP backend, a mixin of
 :class:`~.hip_ops.HipOps` (csrc/scene_kernels.hip): a file scene's objects
-evaluated at a component's material stencil and averaged, in one launch.
+evaluated at a component's material stencil and averaged, in one launch; a
+scene with meshes through the kernel's mesh form and its triangle tables.
 Everything is validated before the launch; a missing kernel is an error.
 """
 
@@ -10,7 +11,8 @@ import ctypes
 
 import torch
 
-from ..layout.scene_file import SCENE_ENT_SIZE, SCENE_MAX_OBJECTS, SceneTable, sample_args
+from ..layout.scene_file import (SCENE_ENT_SIZE, SCENE_MAX_OBJECTS, SCENE_MAX_TRIANGLES, SceneTable,
+                                 sample_args)
 from .hip_lib import HipError, _check, _ptr, _stream, c_double, c_int
 
 
@@ -32,16 +34,38 @@ class HipSceneOps:
             dev = table.device_tables[key] = host.to(self.device)
         return dev
 
+    def _scene_triangles(self, table: SceneTable):
+        """(triangles, ranges) of a table with meshes on the device: 72 bytes
+        a triangle (at least one, so never a null pointer), two ints an
+        object; cached on ``table`` per device."""
+        raw = self.lib.raw
+        if int(raw.fdtd_scene_tri_size()) != 72 or int(raw.fdtd_scene_max_triangles()) != SCENE_MAX_TRIANGLES:
+            raise HipError("SceneTri layout mismatch")
+        key = str(torch.device(self.device)) + " triangles"
+        dev = table.device_tables.get(key)
+        if dev is None:
+            tris = torch.zeros((max(1, len(table.tris)), 9), dtype=torch.float64)
+            tris[:len(table.tris)] = torch.from_numpy(table.tris.reshape(-1, 9).copy())
+            ranges = torch.zeros((max(1, len(table)), 2), dtype=torch.int32)
+            ranges[:len(table)] = torch.from_numpy(table.ranges.copy())
+            dev = table.device_tables[key] = (tris.to(self.device), ranges.to(self.device))
+        return dev
+
     def scene_sample(self, table, quantity: str, points, origin, shape, stride, mod, out=None,
                      cull: bool = True) -> torch.Tensor:
         """The contract of ``TorchOps.scene_sample`` in ONE launch of
-        k_scene_sample.  ``out``: a contiguous fp64 device tensor of ``shape``
+        k_scene_sample (k_scene_sample_mesh when the table holds a mesh).  ``out``: a contiguous fp64 device tensor of ``shape``
         to fill (allocated otherwise); ``cull`` = False evaluates every object
         at every cell (measurements)."""
         if not isinstance(table, SceneTable):
             raise HipError("scene_sample: a SceneTable, got %r" % type(table).__name__)
         if len(table) > SCENE_MAX_OBJECTS:
             raise HipError("scene_sample: %d objects, the table holds %d" % (len(table), SCENE_MAX_OBJECTS))
+        meshes = table.has_meshes()
+        if meshes and len(table.tris) > SCENE_MAX_TRIANGLES:
+            raise HipError("scene_sample: %d triangles, a scene holds %d" % (len(table.tris), SCENE_MAX_TRIANGLES))
+        if meshes and table.range_error():
+            raise HipError("scene_sample: " + table.range_error())
         try:
             q, pts, origin, shape, stride, mod = sample_args(quantity, points, origin, shape, stride, mod)
         except ValueError as e:
@@ -58,10 +82,16 @@ class HipSceneOps:
         tab = self._scene_table(table)
         i3 = ctypes.c_int * 3
         flat = [v for p in pts for v in p]
-        f = self.lib.raw.fdtd_scene_sample
+        args = (_ptr(tab), c_int(len(table)), c_int(q), (ctypes.c_int * len(flat))(*flat), c_int(len(pts)),
+                i3(*origin), i3(*shape), i3(*stride), c_double(mod), c_int(1 if cull else 0), _ptr(out), _stream())
+        if meshes:
+            tris, ranges = self._scene_triangles(table)
+            f = self.lib.raw.fdtd_scene_sample_mesh
+            args += (_ptr(tris), c_int(len(table.tris)), _ptr(ranges))
+        else:
+            f = self.lib.raw.fdtd_scene_sample
         f.restype = c_int
-        rc = f(_ptr(tab), c_int(len(table)), c_int(q), (ctypes.c_int * len(flat))(*flat), c_int(len(pts)),
-               i3(*origin), i3(*shape), i3(*stride), c_double(mod), c_int(1 if cull else 0), _ptr(out), _stream())
+        rc = f(*args)
         _check(rc, "scene_sample")
         self.launches += 1
         return out

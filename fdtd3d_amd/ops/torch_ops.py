@@ -697,10 +697,12 @@ class TorchOps:
         csrc/scene_kernels.hip keeps, the square roots correctly (``_sqrt_rn``):
         this is its oracle."""
         from ..layout.approximation import approximate_material
-        from ..layout.scene_file import (FLAG_IGNORE_SHIFT, FLAG_SHARP, KIND_BOX, KIND_SPHERE, SceneTable,
-                                         sample_args)
+        from ..layout.scene_file import (FLAG_IGNORE_SHIFT, FLAG_SHARP, KIND_BOX, KIND_MESH, KIND_SPHERE,
+                                         SceneTable, sample_args)
         if not isinstance(table, SceneTable):
             raise ValueError("scene_sample: a SceneTable, got %r" % type(table).__name__)
+        if table.has_meshes() and table.range_error():
+            raise ValueError("scene_sample: " + table.range_error())
         q, pts, origin, shape, stride, mod = sample_args(quantity, points, origin, shape, stride, mod)
         dev = self.device if out is None else out.device
         if out is not None and (out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous()):
@@ -711,7 +713,7 @@ class TorchOps:
                    + (stride[d] * origin[d] + off[d])).to(torch.float64) + 0.5 for d in range(3)]
             P = torch.meshgrid(ax[0], ax[1], ax[2], indexing="ij")
             val = torch.full(shape, 1.0 if q == 0 else 0.0, dtype=torch.float64, device=dev)
-            for e in table.ents:
+            for n, e in enumerate(table.ents):
                 flags = int(e["flags"])
                 skip = [bool((flags >> (FLAG_IGNORE_SHIFT + a)) & 1) for a in range(3)]
                 a0 = [float(v) * mod for v in e["p"]]
@@ -723,6 +725,10 @@ class TorchOps:
                             continue
                         t = torch.maximum(a0[a] - P[a], P[a] - b0[a])
                         d = t if d is None else torch.maximum(d, t)
+                elif e["kind"] == KIND_MESH:
+                    t0, tn = (int(v) for v in table.ranges[n])
+                    d = _mesh_distance(table.tris[t0:t0 + tn] * mod, ax, shape,
+                                       q == 0 and not flags & FLAG_SHARP)
                 elif e["kind"] == KIND_SPHERE:
                     sq = [torch.zeros_like(P[a]) if skip[a] else (P[a] - a0[a]) * (P[a] - a0[a]) for a in range(3)]
                     d = _sqrt_rn((sq[0] + sq[1]) + sq[2]) - b0[0]
@@ -752,6 +758,111 @@ class TorchOps:
             return res.contiguous()
         out.copy_(res)
         return out
+
+
+def _mesh_distance(tris, ax, shape, magnitude: bool) -> torch.Tensor:
+    """The signed distance of a closed triangle mesh at the points ``ax[0] x
+    ax[1] x ax[2]``: ``tris`` = (n, 3, 3) fp64 numpy, already scaled, every
+    triangle's vertices v0 <= v1 <= v2 in (x, y, z) order (layout/scene_file.py
+    ``Mesh``).  The oracle of scene_kernels.hip ``mesh_parity`` and
+    ``mesh_dist2``, the same expressions in the same order.
+
+    Sign: a point is inside when a ray along +z crosses an odd number of
+    triangles.  A triangle is crossed when the point lies in its bounding box
+    in x and y and not above it, on the inner side of its three projected
+    edges -- edge functions ``e = (v.x - u.x) * (p.y - u.y) - (v.y - u.y) *
+    (p.x - u.x)`` from the lower vertex u to the higher one v, so the two
+    triangles of an edge see one value, and ``e >= 0`` counts as left of it
+    in both: the ray displaced by (-e^2, +e) -- and below its plane.
+    Triangles with zero projected area never count.
+
+    Magnitude (``magnitude``; +-1 otherwise): the distance to the closest
+    point of the closest triangle, by the regions of that point (vertex,
+    edge, face).  Triangles that cannot come within half a cell of any point
+    are left out, so beyond 0.5 the value is only a lower bound."""
+    import numpy as np
+    dev = ax[0].device
+    par = torch.zeros(shape, dtype=torch.bool, device=dev)
+    dmin = torch.full(shape, float("inf"), dtype=torch.float64, device=dev)
+    if 0 in shape or len(tris) == 0:
+        return dmin if magnitude else torch.ones_like(dmin)
+    X, Y, Z = ax[0].reshape(1, -1, 1, 1), ax[1].reshape(1, 1, -1, 1), ax[2].reshape(1, 1, 1, -1)
+    rlo, rhi = [float(a[0]) for a in ax], [float(a[-1]) for a in ax]
+    lo, hi = tris.min(axis=1), tris.max(axis=1)
+    hit = ((hi[:, 0] >= rlo[0]) & (lo[:, 0] <= rhi[0]) & (hi[:, 1] >= rlo[1]) & (lo[:, 1] <= rhi[1])
+           & (hi[:, 2] >= rlo[2]))
+    near = np.ones(len(tris), dtype=bool)
+    for c in range(3):
+        near &= ~((lo[:, c] - rhi[c] > 1.0) | (rlo[c] - hi[:, c] > 1.0))
+    chunk = max(1, (1 << 18) // (shape[0] * shape[1] * shape[2]))
+
+    def columns(t):
+        """v[i][c], bounding box lo / hi: (chunk, 1, 1, 1) tensors"""
+        def col(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev).reshape(-1, 1, 1, 1)
+        return ([[col(t[:, i, c]) for c in range(3)] for i in range(3)],
+                [col(t[:, :, c].min(axis=1)) for c in range(3)], [col(t[:, :, c].max(axis=1)) for c in range(3)])
+
+    def dot(u, w):
+        return (u[0] * w[0] + u[1] * w[1]) + u[2] * w[2]
+
+    def normal(ab, ac):
+        return [ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]]
+
+    T = tris[hit]
+    for s in range(0, len(T), chunk):
+        (v0, v1, v2), blo, bhi = columns(T[s:s + chunk])
+        ab, ac, bc = ([b - a for a, b in zip(u, w)] for u, w in ((v0, v1), (v0, v2), (v1, v2)))
+        n = normal(ab, ac)
+        ap = [X - v0[0], Y - v0[1], Z - v0[2]]
+        bp = [X - v1[0], Y - v1[1]]
+        l01 = ab[0] * ap[1] - ab[1] * ap[0] >= 0
+        l02 = ac[0] * ap[1] - ac[1] * ap[0] >= 0
+        l12 = bc[0] * bp[1] - bc[1] * bp[0] >= 0
+        up, down = n[2] > 0, n[2] < 0
+        inside = (up & l01 & l12 & ~l02) | (down & ~l01 & ~l12 & l02)
+        box = (X >= blo[0]) & (X <= bhi[0]) & (Y >= blo[1]) & (Y <= bhi[1]) & (Z <= bhi[2])
+        tt = dot(n, ap)
+        crossed = inside & box & ((up & (tt < 0)) | (down & (tt > 0)))
+        par ^= (crossed.sum(dim=0) % 2).bool()
+    if not magnitude:
+        return torch.where(par, -torch.ones_like(dmin), torch.ones_like(dmin))
+
+    T = tris[near]
+    for s in range(0, len(T), chunk):
+        (v0, v1, v2), _, _ = columns(T[s:s + chunk])
+        ab, ac, bc = ([b - a for a, b in zip(u, w)] for u, w in ((v0, v1), (v0, v2), (v1, v2)))
+        n = normal(ab, ac)
+        nn = dot(n, n)
+        full = (len(v0[0]),) + tuple(shape)
+        ap, bp, cp = ([(X - v[0]).expand(full), (Y - v[1]).expand(full), (Z - v[2]).expand(full)]
+                      for v in (v0, v1, v2))
+        d1, d2, d3, d4, d5, d6 = dot(ab, ap), dot(ac, ap), dot(ab, bp), dot(ac, bp), dot(ab, cp), dot(ac, cp)
+        vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+        d43, d56 = d4 - d3, d5 - d6
+        tt = dot(n, ap)
+        zero, one = torch.zeros_like(d1), torch.ones_like(d1)
+        # the regions of the closest point, the last one that holds winning: face, then the edges
+        # v1v2, v0v2, the vertex v2, the edge v0v1, the vertices v1, v0
+        num, den, face = tt * tt, nn.expand(full), torch.ones_like(d1, dtype=torch.bool)
+        r, e = ap, ab
+        for cond, num_c, den_c, r_c, e_c in (
+                ((va <= 0) & (d43 >= 0) & (d56 >= 0), d43, d43 + d56, bp, bc),
+                ((vb <= 0) & (d2 >= 0) & (d6 <= 0), d2, d2 - d6, ap, ac),
+                ((d6 >= 0) & (d5 <= d6), zero, one, cp, ac),
+                ((vc <= 0) & (d1 >= 0) & (d3 <= 0), d1, d1 - d3, ap, ab),
+                ((d3 >= 0) & (d4 <= d3), zero, one, bp, ab),
+                ((d1 <= 0) & (d2 <= 0), zero, one, ap, ab)):
+            num, den, face = torch.where(cond, num_c, num), torch.where(cond, den_c, den), face & ~cond
+            r = [torch.where(cond, a, b) for a, b in zip(r_c, r)]
+            e = [torch.where(cond, a.expand(full), b.expand(full)) for a, b in zip(e_c, e)]
+        x = num / den
+        qv = [a - x * b for a, b in zip(r, e)]
+        ds = torch.where(face, x, dot(qv, qv))
+        ds = torch.where(ds == ds, ds, torch.full_like(ds, float("inf")))   # (a NaN never lowers the minimum)
+        dmin = torch.minimum(dmin, ds.amin(dim=0))
+    dist = _sqrt_rn(dmin)
+    return torch.where(par, -dist, dist)
 
 
 def _sqrt_rn(t: torch.Tensor) -> torch.Tensor:

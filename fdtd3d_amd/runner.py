@@ -406,6 +406,9 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                 rec["probes"] = probes_info
             if scheme.cfg.scene == "file":
                 rec["scene"] = {"objects": len(scheme.scene.objects)}
+                triangles = sum(len(o.mesh) for o in scheme.scene.objects if o.mesh is not None)
+                if triangles:   # (a scene with meshes: their triangles)
+                    rec["scene"]["triangles"] = triangles
             if breakdown is not None:
                 rec["rank0_passes"] = breakdown  # decomposed passes: interior / exchange wait / shell ms
             if scheme.device.type == "cuda":

@@ -1,0 +1,247 @@
+"""Triangle meshes in file scenes on the device: k_scene_sample_mesh
+(csrc/scene_kernels.hip) against the torch op evaluated on the CPU, what it
+leaves untouched, its refusals, and a run end to end from a binary STL."""
+
+import ctypes
+import dataclasses
+import io
+import json
+
+import numpy as np
+import pytest
+import torch
+
+from fdtd3d_amd.layout.scene_file import SCENE_MAX_TRIANGLES, build_table
+from fdtd3d_amd.layout.yee import MATERIAL_STENCIL, MATERIAL_STENCIL_DOUBLE
+from fdtd3d_amd.models.scheme import SchemeConfig, YeeScheme
+from fdtd3d_amd.ops import make_ops
+from fdtd3d_amd.ops.hip_lib import HipError
+from mesh_shapes import icosphere, octahedron, write_binary_stl
+
+pytestmark = pytest.mark.gpu
+
+FREQ = 1.5e10
+SENTINEL = -777.25
+
+
+@pytest.fixture(scope="module")
+def hip(gpu):
+    return make_ops("hip", None, gpu, torch.float64)
+
+
+@pytest.fixture(scope="module")
+def oracle():
+    return make_ops("torch", None, "cpu", torch.float64)
+
+
+def stencil(comp, mod):
+    if mod == 1:
+        return list(MATERIAL_STENCIL[comp])
+    return [tuple(2 * b[a] + s[a] for a in range(3)) for b, s in MATERIAL_STENCIL_DOUBLE[comp]]
+
+
+def mesh(vt, **kw):
+    return dict({"shape": "mesh", "vertices": vt[0], "triangles": vt[1]}, **kw)
+
+
+def scene(origin, shape, mod):
+    """In cells (eps-grid extent / mod): an octahedron on sample coordinates,
+    an 80-triangle icosphere across two faces of the region, a sphere over
+    part of it, a mesh over the sphere."""
+    lo = [float(o) for o in origin]
+    hi = [float(o + s) for o, s in zip(origin, shape)]
+    mid = [float(round((a + b) / 2)) + 0.5 for a, b in zip(lo, hi)]
+    r = min(2.0 + min(shape) // 4, 4.0)
+    return [mesh(octahedron(mid, r), eps=2.25, omega_p=0.7),
+            mesh(icosphere((hi[0] - 0.63, lo[1] + 0.41, mid[2] + 0.27), 2.37, 1), eps=5.0, omega_p=1.25),
+            {"shape": "sphere", "center": [hi[0] - 1.7, lo[1] + 1.37, mid[2] + 1.3], "radius": 1.73, "eps": 1.7},
+            mesh(octahedron((hi[0] - 1.21, lo[1] + 1.63, mid[2] + 0.77), 1.41), eps=3.5, omega_p=0.5)]
+
+
+REGIONS = [((9, 7, 11), (3, -2, 5)), ((5, 3, 130), (-4, 6, 1))]
+
+
+@pytest.mark.parametrize("mod", [1, 2])
+@pytest.mark.parametrize("shape,origin", REGIONS, ids=["9x7x11", "5x3x130"])
+def test_kernel_equals_oracle(hip, oracle, shape, origin, mod):
+    """8. torch.equal with the torch op on the CPU: several rows per wave and
+    one row with an odd tail, every stencil size, both quantities and
+    smoothings, meshes under and over other objects; one launch per call;
+    the same bits without culling."""
+    objs = scene(origin, shape, mod)
+    stride = (mod, mod, mod)
+    cases = [[(0, 0, 0)], stencil("Ex", 1), stencil("Hx", 1), stencil("Ey", 2), stencil("Hy", 2)]
+    assert {len(c) for c in cases} == {1, 2, 4, 8}
+    for smoothing in ("linear", "none"):
+        tab = build_table(objs, "3d", smoothing, FREQ)
+        assert len(tab.tris) == 8 + 80 + 8
+        for pts in cases:
+            for q in ("eps", "omega"):
+                want = oracle.scene_sample(tab, q, pts, origin, shape, stride, float(mod))
+                n0 = hip.launches
+                got = hip.scene_sample(tab, q, pts, origin, shape, stride, float(mod))
+                assert hip.launches == n0 + 1
+                assert got.dtype == torch.float64 and tuple(got.shape) == shape and got.is_cuda
+                assert torch.equal(got.cpu(), want), (smoothing, len(pts), q, int((got.cpu() != want).sum()))
+                assert len(torch.unique(want)) >= 4, "trivial scene"
+                all_tris = hip.scene_sample(tab, q, pts, origin, shape, stride, float(mod), cull=False)
+                assert torch.equal(all_tris, got), (smoothing, len(pts), q, "culling changed the result")
+
+
+def test_larger_mesh_and_far_meshes(hip, oracle):
+    """9. 1 280 triangles at one stencil; meshes far from the region leave vacuum."""
+    shape, origin = (9, 7, 11), (3, -2, 5)
+    ball = mesh(icosphere((7.63, 1.41, 10.27), 3.37, 3), eps=5.0, omega_p=1.25)
+    assert len(ball["triangles"]) == 1280
+    for smoothing in ("linear", "none"):
+        tab = build_table([ball], "3d", smoothing, FREQ)
+        for q in ("eps", "omega"):
+            want = oracle.scene_sample(tab, q, stencil("Hx", 1), origin, shape, (1, 1, 1), 1.0)
+            got = hip.scene_sample(tab, q, stencil("Hx", 1), origin, shape, (1, 1, 1), 1.0)
+            assert torch.equal(got.cpu(), want), (smoothing, q)
+            assert len(torch.unique(want)) >= (4 if (q, smoothing) == ("eps", "linear") else 3)
+    far = [mesh(icosphere((200.3, -150.7, 90.37), 4.37, 1), eps=3.0, omega_p=1.0),
+           mesh(octahedron((7.5, 1.5, 60.5), 3.0), eps=2.0, omega_p=1.0),     # above: the region's rays cross it twice
+           mesh(octahedron((7.5, 1.5, -40.5), 3.0), eps=2.0, omega_p=1.0)]    # below the region, the same columns
+    tab = build_table(far, "3d", "linear", FREQ)
+    for q, vacuum in (("eps", 1.0), ("omega", 0.0)):
+        for cull in (True, False):
+            got = hip.scene_sample(tab, q, stencil("Hx", 1), origin, shape, (1, 1, 1), 1.0, cull=cull)
+            assert bool((got == vacuum).all()), (q, cull)
+
+
+@pytest.mark.parametrize("shape", [(5, 3, 130), (9, 7, 11)], ids=["even-z", "odd-z"])
+def test_only_the_region_is_written(hip, oracle, gpu, shape):
+    """10. The region as a window of a larger sentinel-filled buffer, 16-byte
+    aligned or not: the cells before and after it stay untouched."""
+    origin = (2, 1, -3)
+    tab = build_table(scene(origin, shape, 1), "3d", "linear", FREQ)
+    n = shape[0] * shape[1] * shape[2]
+    want = oracle.scene_sample(tab, "eps", stencil("Hy", 1), origin, shape, (1, 1, 1), 1.0)
+    for pad in (512, 513):
+        buf = torch.full((n + 2 * pad,), SENTINEL, dtype=torch.float64, device=gpu)
+        out = buf[pad:pad + n].view(shape)
+        got = hip.scene_sample(tab, "eps", stencil("Hy", 1), origin, shape, (1, 1, 1), 1.0, out=out)
+        assert got.data_ptr() == out.data_ptr()
+        assert torch.equal(out.cpu(), want)
+        assert bool((buf[:pad] == SENTINEL).all()) and bool((buf[pad + n:] == SENTINEL).all())
+
+
+def test_refusals_launch_nothing(hip, gpu):
+    """10. A range past the table, more triangles than a scene holds, and at
+    the entry point a null triangle or range pointer or a bad count: the launch
+    count and the output stay as they were."""
+    shape, origin = (4, 3, 6), (0, 0, 0)
+    tab = build_table(scene(origin, shape, 1), "3d", "linear", FREQ)
+    out = torch.full(shape, SENTINEL, dtype=torch.float64, device=gpu)
+    n0 = hip.launches
+    args = ("eps", [(0, 0, 0)], origin, shape, (1, 1, 1), 1.0)
+
+    def refused(table, match):
+        with pytest.raises(HipError, match=match):
+            hip.scene_sample(table, *args, out=out)
+        assert hip.launches == n0 and bool((out == SENTINEL).all())
+
+    past = build_table(scene(origin, shape, 1), "3d", "linear", FREQ)
+    past.ranges[3, 1] += 1
+    refused(past, "range past")
+    past.ranges[3] = (-1, 2)
+    refused(past, "range past")
+    many = build_table(scene(origin, shape, 1), "3d", "linear", FREQ)
+    many.tris = np.broadcast_to(many.tris[:1], (SCENE_MAX_TRIANGLES + 1, 3, 3))   # (a view: nothing that size exists)
+    refused(many, "a scene holds")
+
+    f = hip.lib.raw.fdtd_scene_sample_mesh
+    f.restype = ctypes.c_int
+    i3 = ctypes.c_int * 3
+    dev_tab = hip._scene_table(tab)
+    tris, ranges = hip._scene_triangles(tab)
+    assert tuple(tris.shape) == (len(tab.tris), 9) and tuple(ranges.shape) == (len(tab), 2)
+
+    def entry(tris_p=tris.data_ptr(), ntris=len(tab.tris), ranges_p=ranges.data_ptr(), out_p=out.data_ptr()):
+        vp = ctypes.c_void_p
+        return f(vp(dev_tab.data_ptr()), ctypes.c_int(len(tab)), ctypes.c_int(0), i3(0, 0, 0), ctypes.c_int(1),
+                 i3(*origin), i3(*shape), i3(1, 1, 1), ctypes.c_double(1.0), ctypes.c_int(1), vp(out_p),
+                 vp(torch.cuda.current_stream().cuda_stream), vp(tris_p), ctypes.c_int(ntris), vp(ranges_p))
+
+    for kw in (dict(tris_p=None), dict(ranges_p=None), dict(ntris=-1), dict(ntris=SCENE_MAX_TRIANGLES + 1),
+               dict(out_p=None)):
+        assert entry(**kw) == 1, kw   # hipErrorInvalidValue
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all())
+    assert entry() == 0
+    torch.cuda.synchronize()
+    assert not bool((out == SENTINEL).any())
+
+
+# ------------------------------------------------------------------ end to end
+def _run(cfg, backend, device):
+    dt = torch.float32 if cfg.dtype == "f32" else torch.float64
+    s = YeeScheme(cfg, make_ops(backend, None, device, dt))
+    s.init_scheme()
+    s.init_grids()
+    s.perform_steps()
+    if device != "cpu":
+        torch.cuda.synchronize()
+    return s
+
+
+@pytest.fixture(scope="module")
+def stl_scene(tmp_path_factory):
+    """A scene file beside its binary STL: an icosphere of 320 triangles."""
+    d = tmp_path_factory.mktemp("mesh")
+    write_binary_stl(str(d / "ball.stl"), *icosphere((0.0, 0.0, 0.0), 1.0, 2))
+    p = d / "scene.json"
+    p.write_text(json.dumps({"objects": [{"shape": "mesh", "file": "ball.stl", "scale": 5.37,
+                                          "translate": [16.3, 15.7, 16.37], "eps": 4.0}]}))
+    return p
+
+
+@pytest.fixture(scope="module")
+def oracle_run(stl_scene):
+    cfg = SchemeConfig(scheme="3d", size=(32, 32, 32), time_steps=12, dtype="f64", use_pml=True, pml_type="cpml",
+                       pml_size=(2, 2, 2), use_tfsf=True, tfsf_size=(4, 4, 4), scene="file",
+                       scene_file=str(stl_scene), hybrid_block=1, time_block=1)
+    return cfg, _run(cfg, "torch", "cpu")
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_stl_run_vs_fp64_oracle(gpu, oracle_run, dtype):
+    """11. 32^3 CPML + TF/SF with a dielectric icosphere from a binary STL, hybrid
+    passes on HIP against the fp64 CPU oracle of the same scene, at the
+    tolerances of test_scene_gpu.py test_multi_object_run_vs_fp64_oracle
+    (hybrid: 10 x 2e-5 fp32, 10 x 1e-12 fp64).  (2-cell layers and 2-step
+    passes: with thicker layers the hybrid planner rejects a 32^3 grid.)"""
+    cfg, b = oracle_run
+    # (faces in the blocked core: with them in the shell the fp32 CPML plan leaves a 32^3 grid too small a core)
+    a = _run(dataclasses.replace(cfg, dtype=dtype, use_fused=True, hybrid_block=2, time_block=0,
+                                 hybrid_tfsf="core"), "hip", gpu)
+    assert a.hybrid is not None, "the run took single steps only"
+    assert len(a.scene.table().tris) == 320
+    tol = 2e-4 if dtype == "f32" else 1e-11
+    for c in a.comps:
+        scale = max(float(b.F[0][o].abs().max()) for o in b.comps if o[0] == c[0]) + 1e-300
+        err = float((a.F[0][c].double().cpu() - b.F[0][c]).abs().max())
+        print("%s %s: err %.3g of scale %.3g (tol %.1g)" % (dtype, c, err, scale, tol))
+        assert err <= tol * scale, (c, err, scale)
+    assert float(b.F[0]["Ez"].abs().max()) > 0
+
+
+def test_save_materials(gpu, tmp_path, stl_scene):
+    """11. --save-materials on HIP writes the Eps grid the torch backend
+    writes; the --json line counts the triangles."""
+    from fdtd3d_amd.runner import run
+    files = {}
+    for backend, device in (("hip", "cuda"), ("torch", "cpu")):
+        d = tmp_path / backend
+        d.mkdir()
+        out = io.StringIO()
+        argv = ["--3d", "--sizex", "32", "--same-size", "--time-steps", "2", "--backend", backend, "--device", device,
+                "--scene", "file", "--scene-file", str(stl_scene), "--json", "--save-materials", "--save-as-dat",
+                "--output-dir", str(d), "--dtype", "f32"]
+        assert run(argv, out=out) == 0, out.getvalue()
+        assert json.loads(out.getvalue().strip().splitlines()[-1])["scene"] == {"objects": 1, "triangles": 320}
+        files[backend] = {f.name: f.read_bytes() for f in d.iterdir() if "Eps" in f.name}
+    assert files["hip"] and files["hip"].keys() == files["torch"].keys()
+    for name, data in files["hip"].items():
+        assert data == files["torch"][name], name
