@@ -258,4 +258,20 @@ int fdtd_energy_ent_size();
 int fdtd_probe_sample_f32(const void* tab, int nslots, void* series, int row, int capacity, void* s);
 int fdtd_probe_sample_f64(const void* tab, int nslots, void* series, int row, int capacity, void* s);
 int fdtd_probe_ent_size();
+
+// file scenes (scene_kernels.hip): the magnetic Drude plasma frequency and the
+// collision frequencies of a component.  tab, points, origin, shape, stride,
+// mod, cull, out as fdtd_scene_sample; quantity 2 = omega_m, 3 = gamma, 4 =
+// gamma_m; drude = ndrude (== nobj) device triples (gamma_e, omega_m, gamma_m)
+// of fdtd_scene_drude_size() bytes, rad/s.  The mesh form adds the triangle
+// tables of fdtd_scene_sample_mesh.  hipErrorInvalidValue, with nothing
+// launched, for a null pointer, another quantity or ndrude != nobj
+int fdtd_scene_sample_drude(const void* tab, int nobj, int quantity, const int* points, int npts, const int* origin,
+                            const int* shape, const int* stride, double mod, int cull, void* out, void* s,
+                            const void* drude, int ndrude);
+int fdtd_scene_sample_drude_mesh(const void* tab, int nobj, int quantity, const int* points, int npts,
+                                 const int* origin, const int* shape, const int* stride, double mod, int cull,
+                                 void* out, void* s, const void* drude, int ndrude, const void* tris, int ntris,
+                                 const void* ranges);
+int fdtd_scene_drude_size();
 }

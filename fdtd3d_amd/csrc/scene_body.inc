@@ -2,6 +2,9 @@
 // SCENE_WITH_MESH 0 / 1: the kernel's parameters tab, out, A (and M, the mesh tables) are in scope.
 // With 0 the preprocessor drops every mesh statement: the kernel of scenes without meshes stays, instruction
 // for instruction, what it was before the fourth kind existed.
+// SCENE_WITH_DRUDE 1 (k_scene_sample_drude and its mesh twin, Q = 2 omega_m, 3 gamma, 4 gamma_m; the
+// parameter drude in scope) compiles in the second table and, for a collision frequency, the damping g painted
+// beside the pole v; with 0 the preprocessor drops those statements too, and eps / omega stay what they were.
 #pragma clang fp contract(off)
 constexpr bool MESH = SCENE_WITH_MESH;
   const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
@@ -37,6 +40,12 @@ constexpr bool MESH = SCENE_WITH_MESH;
   double v[2][SCENE_MAX_POINTS];
 #pragma unroll
   for (int k = 0; k < SCENE_MAX_POINTS; ++k) v[0][k] = v[1][k] = Q == 0 ? 1.0 : 0.0;
+#if SCENE_WITH_DRUDE
+  double g[2][SCENE_MAX_POINTS];
+#pragma unroll
+  for (int k = 0; k < SCENE_MAX_POINTS; ++k) g[0][k] = g[1][k] = 0.0;
+  const mon::ConstTab<SceneDrude> D = (mon::ConstTab<SceneDrude>)drude;
+#endif
 
   const mon::ConstTab<SceneEnt> E = (mon::ConstTab<SceneEnt>)tab;
   for (int o = 0; o < A.nobj; ++o) {
@@ -61,7 +70,14 @@ constexpr bool MESH = SCENE_WITH_MESH;
       }
       if (__builtin_amdgcn_readfirstlane((int)miss)) continue;
     }
+#if SCENE_WITH_DRUDE
+    // the pole a point is painted with (gamma: the electric one, which decides whether the point is
+    // dispersive) and the damping that goes with it
+    const double obj = Q == 3 ? E[o].omega : D[o].omega_m;
+    const double damp = Q == 3 ? D[o].gamma_e : D[o].gamma_m;
+#else
     const double obj = Q == 0 ? E[o].eps : E[o].omega;
+#endif
 #if SCENE_WITH_MESH
     // a mesh: bit 8 j + k of par = the parity of the triangles crossed above point (j, k), dm = the
     // squared distance of the closest one (under linear smoothing)
@@ -142,8 +158,11 @@ constexpr bool MESH = SCENE_WITH_MESH;
         const double d = scene_dist(kind, flags, a, b, P);
 #endif
         const double below = v[j][k];
-        if (Q == 1 || (flags & SCENE_SHARP)) {
+        if (Q >= 1 || (flags & SCENE_SHARP)) {
           v[j][k] = d < 0.0 ? obj : below;
+#if SCENE_WITH_DRUDE
+          if (Q >= 3) g[j][k] = d < 0.0 ? damp : g[j][k];
+#endif
         } else {
           const double prop = 0.5 - d;
           const double mid = prop * obj + (1.0 - prop) * below;
@@ -168,7 +187,7 @@ constexpr bool MESH = SCENE_WITH_MESH;
           for (int k = 0; k + step < SCENE_MAX_POINTS; k += 2 * step) m[k] = (m[k] + m[k + step]) / 2.0;
         }
       res[j] = m[0];
-    } else {
+    } else if (Q <= 2) {
       // sqrt(sum(w * w) / n), the sum left to right from 0 (approximate_drude)
       double s = 0.0;
 #pragma unroll
@@ -176,6 +195,20 @@ constexpr bool MESH = SCENE_WITH_MESH;
         if (k < A.npts) s = s + v[j][k] * v[j][k];
       res[j] = __dsqrt_rn(s / (double)A.npts);
     }
+#if SCENE_WITH_DRUDE
+    else {
+      // sum(g) / count over the dispersive points (pole != 0), both left to right from 0; 0 without one
+      double s = 0.0, n = 0.0;
+#pragma unroll
+      for (int k = 0; k < SCENE_MAX_POINTS; ++k)
+        if (k < A.npts) {
+          s = s + g[j][k];
+          n = n + (v[j][k] != 0.0 ? 1.0 : 0.0);
+        }
+      const double mean = s / (n > 0.0 ? n : 1.0);
+      res[j] = n > 0.0 ? mean : 0.0;
+    }
+#endif
   }
 
   if (y >= A.n[1] || z >= A.n[2]) return;

@@ -28,6 +28,13 @@
 // nothing -- and in the distance only if its box grown by one cell meets the
 // tile: the others lie farther than a cell from every point, which can move a
 // distance only where it stays beyond 0.5 and the painting rule does not read it.
+//
+// The magnetic pole and the collision frequencies (k_scene_sample_drude and its
+// mesh twin, the same body once more) read a second table, an object's
+// (gamma_e, omega_m, gamma_m), the same way.  All are sharp.  A collision
+// frequency paints two values per point, the pole and its damping, and reduces
+// to the mean damping of the points whose pole is not zero (approximate_drude);
+// an object culled for a wave paints neither.
 #include "common.h"
 #include "monitor_dev.h"
 
@@ -47,6 +54,12 @@ struct SceneEnt {
   double omega;  // rad/s
 };
 static_assert(sizeof(SceneEnt) == 72, "SceneEnt layout (layout/scene_file.py SCENE_ENT)");
+
+// what travels beside an entry (layout/scene_file.py SceneTable.drude), rad/s
+struct SceneDrude {
+  double gamma_e, omega_m, gamma_m;
+};
+static_assert(sizeof(SceneDrude) == 24, "SceneDrude layout (layout/scene_file.py SceneTable.drude)");
 
 // a triangle: its vertices in ascending (x, y, z) order (layout/scene_file.py Mesh)
 struct SceneTri {
@@ -187,7 +200,9 @@ template <int Q>  // 0: eps, 1: omega
 __global__ __launch_bounds__(256) void k_scene_sample(const SceneEnt* __restrict__ tab, double* __restrict__ out,
                                                       SceneArgs A) {
 #define SCENE_WITH_MESH 0
+#define SCENE_WITH_DRUDE 0
 #include "scene_body.inc"
+#undef SCENE_WITH_DRUDE
 #undef SCENE_WITH_MESH
 }
 
@@ -195,16 +210,41 @@ template <int Q>
 __global__ __launch_bounds__(256) void k_scene_sample_mesh(const SceneEnt* __restrict__ tab,
                                                            double* __restrict__ out, SceneArgs A, SceneMesh M) {
 #define SCENE_WITH_MESH 1
+#define SCENE_WITH_DRUDE 0
 #include "scene_body.inc"
+#undef SCENE_WITH_DRUDE
 #undef SCENE_WITH_MESH
 }
 
-// the arguments both entry points share, checked and turned into SceneArgs; 0: launch, -1: nothing to do
-int scene_args(const void* tab, int nobj, int quantity, const int* points, int npts, const int* origin,
-               const int* shape, const int* stride, double mod, int cull, void* out, SceneArgs& A) {
+template <int Q>  // 2: omega_m, 3: gamma, 4: gamma_m
+__global__ __launch_bounds__(256) void k_scene_sample_drude(const SceneEnt* __restrict__ tab,
+                                                            const SceneDrude* __restrict__ drude,
+                                                            double* __restrict__ out, SceneArgs A) {
+#define SCENE_WITH_MESH 0
+#define SCENE_WITH_DRUDE 1
+#include "scene_body.inc"
+#undef SCENE_WITH_DRUDE
+#undef SCENE_WITH_MESH
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void k_scene_sample_drude_mesh(const SceneEnt* __restrict__ tab,
+                                                                 const SceneDrude* __restrict__ drude,
+                                                                 double* __restrict__ out, SceneArgs A, SceneMesh M) {
+#define SCENE_WITH_MESH 1
+#define SCENE_WITH_DRUDE 1
+#include "scene_body.inc"
+#undef SCENE_WITH_DRUDE
+#undef SCENE_WITH_MESH
+}
+
+// the arguments the entry points share (quantity one of qlo .. qhi), checked and turned into SceneArgs;
+// 0: launch, -1: nothing to do
+int scene_args(const void* tab, int nobj, int quantity, int qlo, int qhi, const int* points, int npts,
+               const int* origin, const int* shape, const int* stride, double mod, int cull, void* out, SceneArgs& A) {
 
   if (!tab || !points || !origin || !shape || !stride || !out) return (int)hipErrorInvalidValue;
-  if (nobj < 0 || nobj > SCENE_MAX_OBJECTS || (quantity != 0 && quantity != 1)) return (int)hipErrorInvalidValue;
+  if (nobj < 0 || nobj > SCENE_MAX_OBJECTS || quantity < qlo || quantity > qhi) return (int)hipErrorInvalidValue;
   if (npts != 1 && npts != 2 && npts != 4 && npts != 8) return (int)hipErrorInvalidValue;
   if (mod != 1.0 && mod != 2.0) return (int)hipErrorInvalidValue;
   A = SceneArgs{};
@@ -254,7 +294,7 @@ FDTD_API int fdtd_scene_sample(const void* tab, int nobj, int quantity, const in
                                const int* origin, const int* shape, const int* stride, double mod, int cull,
                                void* out, void* s) {
   SceneArgs A;
-  const int rc = scene_args(tab, nobj, quantity, points, npts, origin, shape, stride, mod, cull, out, A);
+  const int rc = scene_args(tab, nobj, quantity, 0, 1, points, npts, origin, shape, stride, mod, cull, out, A);
   if (rc) return rc < 0 ? 0 : rc;
   const unsigned blocks = cdiv(A.waves, 4);
   if (quantity == 0)
@@ -273,7 +313,7 @@ FDTD_API int fdtd_scene_sample_mesh(const void* tab, int nobj, int quantity, con
                                     void* out, void* s, const void* tris, int ntris, const void* ranges) {
   if (ntris < 0 || ntris > SCENE_MAX_TRIANGLES || (ntris > 0 && !tris) || !ranges) return (int)hipErrorInvalidValue;
   SceneArgs A;
-  const int rc = scene_args(tab, nobj, quantity, points, npts, origin, shape, stride, mod, cull, out, A);
+  const int rc = scene_args(tab, nobj, quantity, 0, 1, points, npts, origin, shape, stride, mod, cull, out, A);
   if (rc) return rc < 0 ? 0 : rc;
   const SceneMesh M = {(const SceneTri*)tris, (const SceneRange*)ranges, ntris};
   const unsigned blocks = cdiv(A.waves, 4);
@@ -283,6 +323,52 @@ FDTD_API int fdtd_scene_sample_mesh(const void* tab, int nobj, int quantity, con
     k_scene_sample_mesh<1><<<blocks, 256, 0, (hipStream_t)s>>>((const SceneEnt*)tab, (double*)out, A, M);
   FDTD_RETURN_LAUNCH_STATUS();
 }
+
+// The magnetic plasma frequency and the collision frequencies: quantity 2 = omega_m, 3 = gamma, 4 =
+// gamma_m, `drude` = ndrude device triples (gamma_e, omega_m, gamma_m) of doubles, one per object
+// (ndrude == nobj); everything else as fdtd_scene_sample.
+FDTD_API int fdtd_scene_sample_drude(const void* tab, int nobj, int quantity, const int* points, int npts,
+                                     const int* origin, const int* shape, const int* stride, double mod, int cull,
+                                     void* out, void* s, const void* drude, int ndrude) {
+  if (!drude || ndrude != nobj) return (int)hipErrorInvalidValue;
+  SceneArgs A;
+  const int rc = scene_args(tab, nobj, quantity, 2, 4, points, npts, origin, shape, stride, mod, cull, out, A);
+  if (rc) return rc < 0 ? 0 : rc;
+  const unsigned blocks = cdiv(A.waves, 4);
+  const SceneEnt* T = (const SceneEnt*)tab;
+  const SceneDrude* D = (const SceneDrude*)drude;
+  if (quantity == 2)
+    k_scene_sample_drude<2><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A);
+  else if (quantity == 3)
+    k_scene_sample_drude<3><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A);
+  else
+    k_scene_sample_drude<4><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A);
+  FDTD_RETURN_LAUNCH_STATUS();
+}
+
+// The same for a scene with meshes: `tris`, `ntris`, `ranges` as fdtd_scene_sample_mesh.
+FDTD_API int fdtd_scene_sample_drude_mesh(const void* tab, int nobj, int quantity, const int* points, int npts,
+                                          const int* origin, const int* shape, const int* stride, double mod,
+                                          int cull, void* out, void* s, const void* drude, int ndrude,
+                                          const void* tris, int ntris, const void* ranges) {
+  if (!drude || ndrude != nobj) return (int)hipErrorInvalidValue;
+  if (ntris < 0 || ntris > SCENE_MAX_TRIANGLES || (ntris > 0 && !tris) || !ranges) return (int)hipErrorInvalidValue;
+  SceneArgs A;
+  const int rc = scene_args(tab, nobj, quantity, 2, 4, points, npts, origin, shape, stride, mod, cull, out, A);
+  if (rc) return rc < 0 ? 0 : rc;
+  const SceneMesh M = {(const SceneTri*)tris, (const SceneRange*)ranges, ntris};
+  const unsigned blocks = cdiv(A.waves, 4);
+  const SceneEnt* T = (const SceneEnt*)tab;
+  const SceneDrude* D = (const SceneDrude*)drude;
+  if (quantity == 2)
+    k_scene_sample_drude_mesh<2><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A, M);
+  else if (quantity == 3)
+    k_scene_sample_drude_mesh<3><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A, M);
+  else
+    k_scene_sample_drude_mesh<4><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A, M);
+  FDTD_RETURN_LAUNCH_STATUS();
+}
+FDTD_API int fdtd_scene_drude_size() { return (int)sizeof(SceneDrude); }
 FDTD_API int fdtd_scene_ent_size() { return (int)sizeof(SceneEnt); }
 FDTD_API int fdtd_scene_max_objects() { return (int)SCENE_MAX_OBJECTS; }
 FDTD_API int fdtd_scene_tri_size() { return (int)sizeof(SceneTri); }

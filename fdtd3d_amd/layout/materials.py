@@ -22,7 +22,8 @@ Scenes:
 * ``drude-sphere`` -- one electric Drude sphere (eps_inf = 1, omega_p =
   sqrt(2)*2*pi*f as in the reference scene, gamma = 0) at ``--sphere-center-*``
   with ``--sphere-radius``, in vacuum (BASELINE config 4).
-* ``file`` -- user-defined boxes, spheres and cylinders painted over vacuum
+* ``file`` -- user-defined boxes, spheres, cylinders and meshes painted over vacuum,
+  dielectric or Drude media (electric and magnetic poles, with damping)
   (``--scene-file``; :mod:`.scene_file`).  Such a scene is never evaluated on
   an eps-layout grid: the backend's ``scene_sample`` op writes each component's
   averaged material directly.
@@ -40,6 +41,10 @@ import torch
 from .approximation import approximate_drude, approximate_material, approximate_sphere
 from .scene_file import build_table, check_scheme, load_scene_file, parse_objects
 from .yee import MATERIAL_STENCIL, MATERIAL_STENCIL_DOUBLE, YeeLayout
+
+# a file scene's Drude materials: (scene_sample's quantity, the SceneObject field)
+_FILE_DRUDE = {"omega_pe": ("omega", "omega_p"), "gamma_e": ("gamma", "gamma"),
+               "omega_pm": ("omega_m", "omega_pm"), "gamma_m": ("gamma_m", "gamma_m")}
 
 SQRT2_F32 = float(np.float32(np.sqrt(np.float32(2.0))))  # reference uses sqrtf(2.0)
 
@@ -95,7 +100,8 @@ class Scene:
 
     def is_vacuum(self, metamaterials: bool) -> bool:
         if self.kind == "file":
-            return self.uniform("eps") == 1.0 and (not metamaterials or self.uniform("omega_pe") == 0.0)
+            return self.uniform("eps") == 1.0 and (not metamaterials or (self.uniform("omega_pe") == 0.0
+                                                                         and self.uniform("omega_pm") == 0.0))
         if self.kind == "vacuum" or (self.kind == "drude-sphere" and not metamaterials):
             return True
         if self.kind == "reference" and self.scheme != "3d" and not metamaterials:
@@ -130,8 +136,8 @@ class Scene:
         two_d_ref = self.kind == "reference" and self.scheme != "3d"
         if self.kind == "file" and name == "eps":
             return None if any(o.eps != 1.0 for o in self.objects) else 1.0
-        if self.kind == "file" and name == "omega_pe":
-            return None if any(o.omega_p != 0.0 for o in self.objects) else 0.0
+        if self.kind == "file" and name in _FILE_DRUDE:
+            return None if any(getattr(o, _FILE_DRUDE[name][1]) != 0.0 for o in self.objects) else 0.0
         if name == "eps":
             return 1.0 if self.kind in ("vacuum", "drude-sphere") or two_d_ref else None
         if name == "mu":
@@ -210,7 +216,7 @@ class MaterialSampler:
     def grid(self, name: str) -> torch.Tensor:
         if name not in self._cache and self.scene.kind == "file":
             lo, shp = self._eps_region()
-            if name in ("eps", "omega_pe"):
+            if name == "eps" or name in _FILE_DRUDE:
                 self._cache[name] = self._sample(name, [(0, 0, 0)], lo, shp, (1, 1, 1))
             else:
                 self._cache[name] = torch.full(shp, 1.0 if name == "mu" else 0.0, dtype=self.dtype, device=self.device)
@@ -241,12 +247,12 @@ class MaterialSampler:
         return _dedupe_points(comp, pts, act, self.double)
 
     def _sample(self, name: str, points, origin, shape, stride) -> torch.Tensor:
-        """A file scene's ``name`` (eps / omega_pe) through the backend op."""
+        """A file scene's ``name`` (eps or a Drude material) through the backend op."""
         if self.ops is None:
             from ..ops.torch_ops import TorchOps
             self.ops = TorchOps(self.layout, self.device, self.dtype)
-        return self.ops.scene_sample(self.scene.table(), "eps" if name == "eps" else "omega", points, origin, shape,
-                                     stride, self.mod)
+        return self.ops.scene_sample(self.scene.table(), "eps" if name == "eps" else _FILE_DRUDE[name][0], points,
+                                     origin, shape, stride, self.mod)
 
     def _stencil(self, comp: str):
         """(points, origin, stride) of component ``comp`` for ``scene_sample``:
@@ -275,11 +281,16 @@ class MaterialSampler:
 
     def averaged_drude(self, comp: str, electric: bool):
         if self.scene.kind == "file":
-            # (gamma = 0 in every file scene: the scalar the callers' expressions take)
-            if not electric:
+            wname, gname = ("omega_pe", "gamma_e") if electric else ("omega_pm", "gamma_m")
+            if self.scene.uniform(wname) == 0.0:
+                # (no pole of this kind, so no damping either)
                 return torch.zeros(self.shape, dtype=self.dtype, device=self.device), 0.0
             pts, origin, stride = self._stencil(comp)
-            return self._sample("omega_pe", pts, origin, self.shape, stride), 0.0
+            w = self._sample(wname, pts, origin, self.shape, stride)
+            # (an undamped scene: the scalar the callers' expressions take)
+            if self.scene.uniform(gname) == 0.0:
+                return w, 0.0
+            return w, self._sample(gname, pts, origin, self.shape, stride)
         w = self._points(comp, self.grid("omega_pe" if electric else "omega_pm"))
         g = self._points(comp, self.grid("gamma_e" if electric else "gamma_m"))
         return approximate_drude(w, g)

@@ -15,7 +15,12 @@ order).  JSON, standard library only::
 Coordinates are in cells on the eps layout (cell centre ``m + 0.5``, the
 convention of ``--sphere-center-*``).  ``eps`` is the relative permittivity
 (default 1), ``omega_p`` the electric Drude plasma frequency in units of
-``2 pi f_source`` (default 0, used with ``--use-metamaterials`` only).  A
+``2 pi f_source`` (default 0, used with ``--use-metamaterials`` only).
+``gamma`` is the collision frequency of that pole, ``omega_pm`` / ``gamma_m``
+the plasma and collision frequencies of a magnetic Drude pole (the same units,
+default 0, sharp like ``omega_p``); a damping needs its pole, so a point is
+dispersive exactly where its plasma frequency is non-zero.  An object sets
+all four Drude values of the points it covers.  ``mu`` is 1 everywhere.  A
 cylinder's ``center`` holds its two in-plane coordinates, in x, y, z order of
 the two axes other than ``axis``; ``span`` is its extent along ``axis``.
 
@@ -63,12 +68,17 @@ KIND_BOX, KIND_SPHERE, KIND_CYLINDER, KIND_MESH = 0, 1, 2, 3
 FLAG_IGNORE_SHIFT = 2
 FLAG_SHARP = 32
 
+# the quantities of ``scene_sample``, by the kernel's index: the plasma frequencies (electric, magnetic) and
+# the collision frequencies of the same poles
+QUANTITIES = ("eps", "omega", "omega_m", "gamma", "gamma_m")
+
 SHAPES = ("box", "sphere", "cylinder", "mesh")
 SMOOTHINGS = ("linear", "none")
-_KEYS = {"box": {"shape", "lo", "hi", "eps", "omega_p"},
-         "sphere": {"shape", "center", "radius", "eps", "omega_p"},
-         "cylinder": {"shape", "axis", "center", "radius", "span", "eps", "omega_p"},
-         "mesh": {"shape", "file", "vertices", "triangles", "scale", "translate", "eps", "omega_p"}}
+_MEDIUM = {"eps", "omega_p", "gamma", "omega_pm", "gamma_m"}
+_KEYS = {"box": {"shape", "lo", "hi"} | _MEDIUM,
+         "sphere": {"shape", "center", "radius"} | _MEDIUM,
+         "cylinder": {"shape", "axis", "center", "radius", "span"} | _MEDIUM,
+         "mesh": {"shape", "file", "vertices", "triangles", "scale", "translate"} | _MEDIUM}
 _AXES = {"x": 0, "y": 1, "z": 2}
 
 
@@ -109,6 +119,9 @@ class SceneObject:
     eps: float = 1.0
     omega_p: float = 0.0
     mesh: Optional[Mesh] = None
+    gamma: float = 0.0      # electric collision frequency, in units of 2 pi f_source like omega_p
+    omega_pm: float = 0.0   # magnetic Drude plasma frequency
+    gamma_m: float = 0.0    # magnetic collision frequency
 
 
 def _number(v, what: str) -> float:
@@ -273,7 +286,7 @@ def parse_object(o, index: int = 0, base_dir: Optional[str] = None) -> SceneObje
     if unknown:
         raise ValueError("scene: object %d (%s) has unknown key %r" % (index, shape, unknown[0]))
     what = "object %d (%s) " % (index, shape)
-    for k in sorted(_KEYS[shape] - {"eps", "omega_p"} - set(o) if shape != "mesh" else ()):
+    for k in sorted(_KEYS[shape] - _MEDIUM - set(o) if shape != "mesh" else ()):
         raise ValueError("scene: %sneeds %r" % (what, k))
     eps = _number(o.get("eps", 1.0), what + "eps")
     omega_p = _number(o.get("omega_p", 0.0), what + "omega_p")
@@ -281,20 +294,29 @@ def parse_object(o, index: int = 0, base_dir: Optional[str] = None) -> SceneObje
         raise ValueError("scene: %seps must be positive, got %r" % (what, eps))
     if omega_p < 0:
         raise ValueError("scene: %somega_p must not be negative, got %r" % (what, omega_p))
+    drude = {}
+    for k in ("gamma", "omega_pm", "gamma_m"):
+        drude[k] = _number(o.get(k, 0.0), what + k)
+        if drude[k] < 0:
+            raise ValueError("scene: %s%s must not be negative, got %r" % (what, k, drude[k]))
+    if drude["gamma"] > 0 and omega_p == 0:
+        raise ValueError("scene: %sgamma needs omega_p > 0: a damping without a pole" % what)
+    if drude["gamma_m"] > 0 and drude["omega_pm"] == 0:
+        raise ValueError("scene: %sgamma_m needs omega_pm > 0: a damping without a pole" % what)
     if shape == "mesh":
         mesh, lo, hi = _mesh(o, what, base_dir)
-        return SceneObject("mesh", lo, hi, eps=eps, omega_p=omega_p, mesh=mesh)
+        return SceneObject("mesh", lo, hi, eps=eps, omega_p=omega_p, mesh=mesh, **drude)
     if shape == "box":
         lo, hi = _vector(o["lo"], 3, what + "lo"), _vector(o["hi"], 3, what + "hi")
         if any(l >= h for l, h in zip(lo, hi)):
             raise ValueError("scene: %sneeds lo < hi on every axis, got %r, %r" % (what, lo, hi))
-        return SceneObject("box", lo, hi, eps=eps, omega_p=omega_p)
+        return SceneObject("box", lo, hi, eps=eps, omega_p=omega_p, **drude)
     radius = _number(o["radius"], what + "radius")
     if radius <= 0:
         raise ValueError("scene: %sradius must be positive, got %r" % (what, radius))
     if shape == "sphere":
         return SceneObject("sphere", _vector(o["center"], 3, what + "center"), radius=radius, eps=eps,
-                           omega_p=omega_p)
+                           omega_p=omega_p, **drude)
     if o["axis"] not in _AXES:
         raise ValueError("scene: %saxis must be x, y or z, got %r" % (what, o["axis"]))
     axis = _AXES[o["axis"]]
@@ -303,7 +325,7 @@ def parse_object(o, index: int = 0, base_dir: Optional[str] = None) -> SceneObje
         raise ValueError("scene: %sneeds span lo < hi, got %r" % (what, span))
     a, b, others = [0.0] * 3, [0.0] * 3, [d for d in range(3) if d != axis]
     a[others[0]], a[others[1]], a[axis], b[axis] = c2[0], c2[1], span[0], span[1]
-    return SceneObject("cylinder", tuple(a), tuple(b), radius=radius, axis=axis, eps=eps, omega_p=omega_p)
+    return SceneObject("cylinder", tuple(a), tuple(b), radius=radius, axis=axis, eps=eps, omega_p=omega_p, **drude)
 
 
 def parse_objects(objects: Sequence, smoothing: str = "linear",
@@ -375,10 +397,12 @@ class SceneTable:
     its bounding box in ``p`` / ``q``; its triangles are rows ``ranges[o, 0]``
     to ``ranges[o, 0] + ranges[o, 1]`` of ``tris`` = (n, 3, 3) fp64 (vertices in
     the order of :class:`Mesh`), ``ranges`` = (objects, 2) int32, zero for every
-    other kind.  ``device_tables`` caches the HIP backend's copies, one per
-    device."""
+    other kind.  ``drude`` = (objects, 3) fp64 travels beside the entries: an
+    object's (gamma_e, omega_m, gamma_m) in rad/s, zeros by default.
+    ``device_tables`` caches the HIP backend's copies, one per device."""
 
-    def __init__(self, ents: np.ndarray, tris: Optional[np.ndarray] = None, ranges: Optional[np.ndarray] = None):
+    def __init__(self, ents: np.ndarray, tris: Optional[np.ndarray] = None, ranges: Optional[np.ndarray] = None,
+                 drude: Optional[np.ndarray] = None):
         if ents.dtype != SCENE_ENT or ents.ndim != 1:
             raise ValueError("SceneTable: a 1D array of SCENE_ENT records")
         if len(ents) > SCENE_MAX_OBJECTS:
@@ -391,9 +415,15 @@ class SceneTable:
             raise _too_many_triangles(len(tris))
         if ranges.dtype != np.int32 or ranges.shape != (len(ents), 2):
             raise ValueError("SceneTable: ranges of shape (objects, 2), int32")
+        drude = np.zeros((len(ents), 3), dtype=np.float64) if drude is None else drude
+        if drude.dtype != np.float64 or drude.shape != (len(ents), 3):
+            raise ValueError("SceneTable: drude of shape (objects, 3), float64")
+        if not np.isfinite(drude).all() or (drude < 0).any():
+            raise ValueError("SceneTable: drude values must be finite and not negative")
         self.ents = ents
         self.tris = tris
         self.ranges = ranges
+        self.drude = drude
         self.device_tables = {}
 
     def __len__(self) -> int:
@@ -418,6 +448,7 @@ def build_table(objects: Sequence[SceneObject], scheme: str = "3d", smoothing: s
     check_scheme(objects, scheme)
     ents = np.zeros(len(objects), dtype=SCENE_ENT)
     ranges = np.zeros((len(objects), 2), dtype=np.int32)
+    drude = np.zeros((len(objects), 3), dtype=np.float64)
     tris, first = [], 0
     ignore = 0 if scheme == "3d" else 4  # 2D: objects ignore z
     for n, (e, o) in enumerate(zip(ents, objects)):
@@ -427,18 +458,19 @@ def build_table(objects: Sequence[SceneObject], scheme: str = "3d", smoothing: s
         e["q"] = o.b if o.shape in ("box", "mesh") else (o.radius, o.b[o.axis], 0.0)
         e["eps"] = o.eps
         e["omega"] = o.omega_p * 2 * math.pi * source_frequency
+        drude[n] = [v * 2 * math.pi * source_frequency for v in (o.gamma, o.omega_pm, o.gamma_m)]
         if o.shape == "mesh":
             ranges[n] = (first, len(o.mesh))
             tris.append(o.mesh.tris)
             first += len(o.mesh)
-    return SceneTable(ents, np.concatenate(tris) if tris else None, ranges)
+    return SceneTable(ents, np.concatenate(tris) if tris else None, ranges, drude)
 
 
 def sample_args(quantity: str, points, origin, shape, stride, mod):
     """The arguments of ``scene_sample`` checked and normalised (both
     backends): (quantity index, points, origin, shape, stride, mod)."""
-    if quantity not in ("eps", "omega"):
-        raise ValueError("scene_sample: quantity eps or omega, got %r" % (quantity,))
+    if quantity not in QUANTITIES:
+        raise ValueError("scene_sample: quantity eps, omega, omega_m, gamma or gamma_m, got %r" % (quantity,))
     pts = [tuple(int(v) for v in p) for p in points]
     if len(pts) not in (1, 2, 4, 8) or any(len(p) != 3 for p in pts):
         raise ValueError("scene_sample: 1, 2, 4 or 8 points of 3 offsets, got %d" % len(pts))
@@ -454,4 +486,4 @@ def sample_args(quantity: str, points, origin, shape, stride, mod):
     reach = max(abs(v) for t in (origin, shape) for v in t) * 2 + max(abs(v) for p in pts for v in p)
     if reach >= 2 ** 30:
         raise ValueError("scene_sample: region beyond 2^30 eps-grid points")
-    return ("eps", "omega").index(quantity), pts, origin, shape, stride, float(mod)
+    return QUANTITIES.index(quantity), pts, origin, shape, stride, float(mod)

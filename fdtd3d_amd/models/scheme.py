@@ -682,15 +682,15 @@ class YeeScheme(BlockedStepping):
                 if cfg.dispersion == "lorentz":
                     w0 = cfg.lorentz_omega0_ratio * 2 * PI * self.source_frequency
                 q = dt * dt * w0 * w0
-                lean = (ue is not None and ug is not None and cfg.scheme == "3d"
+                lean = (ue is not None and cfg.scheme == "3d"
                         and getattr(self.ops, "drude_lut", False) and hasattr(self.ops, "_drude_lut"))
                 lut = None
                 if uw == 0.0 and ug == 0.0:
                     active = None
                 elif lean:
-                    # eps and gamma uniform: the coefficients are a function of
-                    # omega_p alone -- the uint8 index + table built slab by
-                    # slab (_drude_index), never a full-grid fp64 omega grid
+                    # eps uniform: the coefficients are a function of the
+                    # cell's (omega_p, gamma) pair -- the uint8 index + table built
+                    # slab by slab (_drude_index), never a full-grid fp64 omega grid
                     active, lut = self._drude_index(c, dt, e0, eps_c, ug, q, dtp)
                     if lut is None:
                         lean = False  # more than 256 distinct tuples: per-cell arrays
@@ -754,15 +754,16 @@ class YeeScheme(BlockedStepping):
                     self.ops._drude_lut(st, [st[n].cell for n in ("b0", "b1", "b2", "ma1", "ma2")],
                                         self.domain.shape)
 
-    def _drude_index(self, c: str, dt: float, e0: float, eps_c, ug: float, q: float, dtp,
+    def _drude_index(self, c: str, dt: float, e0: float, eps_c, ug: Optional[float], q: float, dtp,
                      slab_cells: int = 1 << 24):
         """(active mask, (uint8 index, coefficient table)) of the dispersive
-        component ``c`` with uniform eps and gamma: omega_p is sampled and
-        averaged over x slabs of the local region (MaterialSampler on each
-        slab), so the transient is a slab of fp64 grids instead of several
-        full ones (1024^3: ~35 GB).  Pass 1 collects the distinct omega
-        values, pass 2 maps every cell to its table row.  (None for the
-        table when there are more than 256 distinct values.)"""
+        component ``c`` with uniform eps: omega_p (and gamma, where it is not
+        the uniform ``ug``) is sampled and averaged over x slabs of the local
+        region (MaterialSampler on each slab), so the transient is a slab of
+        fp64 grids instead of several full ones (1024^3: ~35 GB).  Pass 1
+        collects the distinct omega values (``ug`` None: the distinct (omega,
+        gamma) pairs), pass 2 maps every cell to its table row.  (None for
+        the table when there are more than 256 distinct rows.)"""
         dom = self.domain
         shape = tuple(dom.shape)
         electric = c[0] == "E"
@@ -774,12 +775,33 @@ class YeeScheme(BlockedStepping):
                 n = min(xc, shape[0] - x0)
                 smp = MaterialSampler(self.layout, self.scene, (dom.origin[0] + x0, dom.origin[1], dom.origin[2]),
                                       (n, shape[1], shape[2]), self.device, ops=self.ops)
-                w, _ = smp.averaged_drude(c, electric)
-                yield x0, n, w
-                del smp, w
+                w, g = smp.averaged_drude(c, electric)
+                if ug is not None:
+                    yield x0, n, w
+                else:
+                    # (an undamped slab sampler returns the scalar 0.0)
+                    g = g if isinstance(g, torch.Tensor) else torch.full_like(w, float(g))
+                    yield x0, n, torch.stack((w.reshape(-1), g.reshape(-1)), 1)
+                del smp, w, g
 
         active = torch.zeros(shape, dtype=torch.bool, device=self.device)
         uniq = None
+        if ug is None:
+            slab = (-1,) + shape[1:]
+            for x0, n, wg in slabs():
+                active[x0:x0 + n] = ((wg[:, 0] != 0) | (wg[:, 1] != 0)).reshape(slab)
+                u = torch.unique(wg, dim=0)
+                uniq = u if uniq is None else torch.unique(torch.cat([uniq, u]), dim=0)
+                if uniq.shape[0] > 256:
+                    return active, None
+            ids = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            for x0, n, wg in slabs():
+                # every pair of the slab is a row of uniq, so the rows of the union are uniq's, in its order
+                rows, inv = torch.unique(torch.cat([uniq, wg]), dim=0, return_inverse=True)
+                assert rows.shape[0] == uniq.shape[0]
+                ids[x0:x0 + n] = inv[uniq.shape[0]:].to(torch.uint8).reshape(slab)
+            tab = torch.stack(_drude_coefs(dt, e0, eps_c, uniq[:, 0], uniq[:, 1], q), 1).to(dtp).contiguous()
+            return active, (ids.contiguous(), tab)
         for x0, n, w in slabs():
             # (a uniform non-zero gamma makes every cell dispersive, like
             # approximate_drude's (w != 0) | (g != 0))

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 
 from ..layout.scene_file import (SCENE_ENT_SIZE, SCENE_MAX_OBJECTS, SCENE_MAX_TRIANGLES, SceneTable,
@@ -51,12 +52,28 @@ class HipSceneOps:
             dev = table.device_tables[key] = (tris.to(self.device), ranges.to(self.device))
         return dev
 
+    def _scene_drude(self, table: SceneTable) -> torch.Tensor:
+        """``table.drude`` on the device: (gamma_e, omega_m, gamma_m) an object,
+        24 bytes (at least one row, so never a null pointer); cached on
+        ``table`` per device."""
+        if int(self.lib.raw.fdtd_scene_drude_size()) != 24:
+            raise HipError("SceneDrude layout mismatch")
+        key = str(torch.device(self.device)) + " drude"
+        dev = table.device_tables.get(key)
+        if dev is None:
+            host = torch.zeros((max(1, len(table)), 3), dtype=torch.float64)
+            host[:len(table)] = torch.from_numpy(table.drude.copy())
+            dev = table.device_tables[key] = host.to(self.device)
+        return dev
+
     def scene_sample(self, table, quantity: str, points, origin, shape, stride, mod, out=None,
                      cull: bool = True) -> torch.Tensor:
         """The contract of ``TorchOps.scene_sample`` in ONE launch of
-        k_scene_sample (k_scene_sample_mesh when the table holds a mesh).  ``out``: a contiguous fp64 device tensor of ``shape``
-        to fill (allocated otherwise); ``cull`` = False evaluates every object
-        at every cell (measurements)."""
+        k_scene_sample (k_scene_sample_mesh when the table holds a mesh;
+        k_scene_sample_drude and its mesh twin for omega_m, gamma and gamma_m,
+        which read ``table.drude`` too).  ``out``: a contiguous fp64 device
+        tensor of ``shape`` to fill (allocated otherwise); ``cull`` = False
+        evaluates every object at every cell (measurements)."""
         if not isinstance(table, SceneTable):
             raise HipError("scene_sample: a SceneTable, got %r" % type(table).__name__)
         if len(table) > SCENE_MAX_OBJECTS:
@@ -66,6 +83,10 @@ class HipSceneOps:
             raise HipError("scene_sample: %d triangles, a scene holds %d" % (len(table.tris), SCENE_MAX_TRIANGLES))
         if meshes and table.range_error():
             raise HipError("scene_sample: " + table.range_error())
+        drude = getattr(table, "drude", None)
+        if (not isinstance(drude, np.ndarray) or drude.dtype != np.float64 or drude.shape != (len(table), 3)
+                or not np.isfinite(drude).all() or (drude < 0).any()):
+            raise HipError("scene_sample: drude of shape (%d, 3), float64, finite and not negative" % len(table))
         try:
             q, pts, origin, shape, stride, mod = sample_args(quantity, points, origin, shape, stride, mod)
         except ValueError as e:
@@ -84,12 +105,15 @@ class HipSceneOps:
         flat = [v for p in pts for v in p]
         args = (_ptr(tab), c_int(len(table)), c_int(q), (ctypes.c_int * len(flat))(*flat), c_int(len(pts)),
                 i3(*origin), i3(*shape), i3(*stride), c_double(mod), c_int(1 if cull else 0), _ptr(out), _stream())
+        raw = self.lib.raw
+        if q >= 2:   # omega_m, gamma, gamma_m: the second table
+            args += (_ptr(self._scene_drude(table)), c_int(len(drude)))
         if meshes:
             tris, ranges = self._scene_triangles(table)
-            f = self.lib.raw.fdtd_scene_sample_mesh
+            f = raw.fdtd_scene_sample_drude_mesh if q >= 2 else raw.fdtd_scene_sample_mesh
             args += (_ptr(tris), c_int(len(table.tris)), _ptr(ranges))
         else:
-            f = self.lib.raw.fdtd_scene_sample
+            f = raw.fdtd_scene_sample_drude if q >= 2 else raw.fdtd_scene_sample
         f.restype = c_int
         rc = f(*args)
         _check(rc, "scene_sample")

@@ -692,7 +692,10 @@ class TorchOps:
         the points at eps-grid index ``stride * (origin + i) + offset`` (centre
         ``+ 0.5``) for every offset of ``points``; at each the objects are
         painted first to last over vacuum, then the points reduce as
-        ``approximate_material`` (eps) or ``approximate_drude`` (omega) do.
+        ``approximate_material`` (eps) or ``approximate_drude`` do: a plasma
+        frequency (omega, omega_m) as sqrt(sum(w * w) / n), a collision
+        frequency (gamma, gamma_m) as sum(g) / count over the points whose
+        plasma frequency of the same kind is not zero, 0 where there is none.
         Every operation is rounded on its own, in the order the kernel of
         csrc/scene_kernels.hip keeps, the square roots correctly (``_sqrt_rn``):
         this is its oracle."""
@@ -707,13 +710,18 @@ class TorchOps:
         dev = self.device if out is None else out.device
         if out is not None and (out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous()):
             raise ValueError("scene_sample: out must be contiguous float64 of shape %s" % (shape,))
-        vals = []
+        vals, damps = [], []
         for off in pts:
             ax = [(torch.arange(shape[d], dtype=torch.int64, device=dev) * stride[d]
                    + (stride[d] * origin[d] + off[d])).to(torch.float64) + 0.5 for d in range(3)]
             P = torch.meshgrid(ax[0], ax[1], ax[2], indexing="ij")
             val = torch.full(shape, 1.0 if q == 0 else 0.0, dtype=torch.float64, device=dev)
+            damp = torch.zeros_like(val) if q >= 3 else None
             for n, e in enumerate(table.ents):
+                # what the object paints: its pole (or eps) and, for a gamma quantity, the pole's damping
+                g_e, w_m, g_m = (float(v) for v in table.drude[n])
+                obj = (float(e["eps"]), float(e["omega"]), w_m, float(e["omega"]), w_m)[q]
+                obj_damp = g_e if q == 3 else g_m
                 flags = int(e["flags"])
                 skip = [bool((flags >> (FLAG_IGNORE_SHIFT + a)) & 1) for a in range(3)]
                 a0 = [float(v) * mod for v in e["p"]]
@@ -739,8 +747,10 @@ class TorchOps:
                     d = _sqrt_rn(db * db + dc * dc) - b0[0]
                     if not skip[ax_c]:
                         d = torch.maximum(d, torch.maximum(a0[ax_c] - P[ax_c], P[ax_c] - b0[1]))
-                if q == 1:
-                    val = torch.where(d < 0, torch.full_like(val, float(e["omega"])), val)
+                if q >= 1:
+                    val = torch.where(d < 0, torch.full_like(val, obj), val)
+                    if q >= 3:
+                        damp = torch.where(d < 0, torch.full_like(damp, obj_damp), damp)
                 elif flags & FLAG_SHARP:
                     val = torch.where(d < 0, torch.full_like(val, float(e["eps"])), val)
                 else:
@@ -750,10 +760,15 @@ class TorchOps:
                     o = torch.where(d < -0.5, torch.full_like(val, eps_in), mid)
                     val = torch.where(d > 0.5, val, o)
             vals.append(val)
+            damps.append(damp)
         if q == 0:
             res = approximate_material(vals)
-        else:
+        elif q <= 2:
             res = _sqrt_rn(sum(w * w for w in vals) / float(len(vals)))
+        else:
+            count = sum((w != 0).to(torch.float64) for w in vals)
+            gsum = sum(damps)
+            res = torch.where(count > 0, gsum / torch.clamp(count, min=1.0), torch.zeros_like(gsum))
         if out is None:
             return res.contiguous()
         out.copy_(res)

@@ -409,6 +409,11 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                 triangles = sum(len(o.mesh) for o in scheme.scene.objects if o.mesh is not None)
                 if triangles:   # (a scene with meshes: their triangles)
                     rec["scene"]["triangles"] = triangles
+                # (Drude media beyond a lossless electric pole: the objects with damping / a magnetic pole)
+                for key, field in (("damped", "gamma"), ("magnetic", "omega_pm")):
+                    count = sum(getattr(o, field) > 0 for o in scheme.scene.objects)
+                    if count:
+                        rec["scene"][key] = count
             if breakdown is not None:
                 rec["rank0_passes"] = breakdown  # decomposed passes: interior / exchange wait / shell ms
             if scheme.device.type == "cuda":

@@ -21,6 +21,13 @@
         linear / eps none / omega), culled and not, and the share of
         (wave, triangle) pairs the per-wave culling lets through
 
+    python tools/scene_bench.py drude [N=256] [objects=16]
+        the Drude quantities of a damped, double-negative version of the
+        scene, per field component (its own stencil, a 1- and a 2-fold eps
+        grid): omega_m, gamma and gamma_m next to omega on the same box in the
+        same process (HIP events over 5 calls after a warm-up call), and
+        whether the torch op on the device gives the kernel's bits
+
 Results: profiles/scene.md.
 """
 import os
@@ -31,7 +38,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fdtd3d_amd.layout.scene_file import build_table  # noqa: E402
-from fdtd3d_amd.layout.yee import MATERIAL_STENCIL_DOUBLE  # noqa: E402
+from fdtd3d_amd.layout.yee import MATERIAL_STENCIL, MATERIAL_STENCIL_DOUBLE  # noqa: E402
 from fdtd3d_amd.models.scheme import SchemeConfig, YeeScheme  # noqa: E402
 from fdtd3d_amd.ops import make_ops  # noqa: E402
 
@@ -85,6 +92,44 @@ def op(n, count):
             del ref
             print("| %d^3 | %d | %d | %s | %.0f | %.0f | %.0f (%.1f) | %s |"
                   % (n, len(tab), len(pts), q, us[0], us[1], ms, peak, same), flush=True)
+
+
+def drude(n, count):
+    dev = "cuda:0"
+    hip = make_ops("hip", None, dev, torch.float64)
+    tor = make_ops("torch", None, dev, torch.float64)
+    objs = scene(n, count)
+    for k, o in enumerate(objs[1:]):   # every sphere a metal: damped, every second one with a damped magnetic pole
+        o.update(omega_p=1.0 + 0.05 * k, gamma=0.1 + 0.02 * k)
+        if k % 2:
+            o.update(omega_pm=0.8 + 0.05 * k, gamma_m=0.05 + 0.01 * k)
+    tab = build_table(objs, "3d", "linear", 1.5e10)
+    shape = (n, n, n)
+    out = torch.empty(shape, dtype=torch.float64, device=dev)
+    print("| region | objects | component | points | omega us | omega_m us | gamma us | gamma_m us | gamma / omega "
+          "| same bits |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for mod in (1, 2):
+        for comp in ("Ex", "Ey", "Ez", "Hx", "Hy", "Hz"):
+            pts = (list(MATERIAL_STENCIL[comp]) if mod == 1 else
+                   [tuple(2 * b[a] + s[a] for a in range(3)) for b, s in MATERIAL_STENCIL_DOUBLE[comp]])
+            us, same = {}, True
+            for q in ("omega", "omega_m", "gamma", "gamma_m"):
+                hip.scene_sample(tab, q, pts, (0, 0, 0), shape, (mod,) * 3, float(mod), out=out)
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                for _ in range(5):
+                    hip.scene_sample(tab, q, pts, (0, 0, 0), shape, (mod,) * 3, float(mod), out=out)
+                b.record()
+                torch.cuda.synchronize()
+                us[q] = a.elapsed_time(b) / 5 * 1e3
+                if comp in ("Ex", "Hz"):   # (the torch op: seconds a call)
+                    same = same and bool(torch.equal(tor.scene_sample(tab, q, pts, (0, 0, 0), shape, (mod,) * 3,
+                                                                      float(mod)), out))
+            print("| %d^3 | %d | %s | %d | %.0f | %.0f | %.0f | %.0f | %.2f | %s |"
+                  % (n, len(tab), comp, len(pts), us["omega"], us["omega_m"], us["gamma"], us["gamma_m"],
+                     us["gamma"] / us["omega"], same if comp in ("Ex", "Hz") else "-"), flush=True)
 
 
 def icosphere(c, r, subdivisions):
@@ -198,6 +243,8 @@ def main(argv):
     count = int(argv[2]) if len(argv) > 2 else 16
     if mode == "op":
         op(n, count)
+    elif mode == "drude":
+        drude(int(argv[1]) if len(argv) > 1 else 256, count)
     elif mode == "mesh":
         mesh(int(argv[1]) if len(argv) > 1 else 256, int(argv[2]) if len(argv) > 2 else 5)
     elif mode == "init":
