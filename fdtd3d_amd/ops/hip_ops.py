@@ -471,12 +471,16 @@ class HipOps(HipMonitorOps, HipSceneOps):
         blocked kernel: (float4 array over the box of cells whose value
         differs from the kind's dominant value -- one (x, y, z, 0) vector per
         cell --, that box, the dominant value).  A kind of one scalar gives
-        (None, empty box, scalar).  Cached on the kind's first Coef."""
+        (None, empty box, scalar).  Cached on the kind's first Coef, for
+        these three Coef objects (like ``_scaled``, a Coef counts as
+        immutable): a dict that shares its first Coef with another but not
+        the other two gets its own arrays."""
         sc = cb[names[0]].scalar
         if all(cb[c].cell is None for c in names) and all(cb[c].scalar == sc for c in names):
             return None, ((0, 0, 0), (0, 0, 0)), sc
         cached = getattr(cb[names[0]], "_sparse4", None)
-        if cached is not None and cached[3] == tuple(shape):
+        if (cached is not None and cached[3] == tuple(shape)
+                and all(a is cb[c] for a, c in zip(cached[4], names))):
             return cached[:3]
         arrs = [self._cell_array(cb[c], shape) for c in names]
         flat = arrs[0].reshape(-1)
@@ -501,7 +505,7 @@ class HipOps(HipMonitorOps, HipSceneOps):
             for n in range(3):
                 v[..., n] = arrs[n][sl]
             out = (v.contiguous(), box, dom)
-        cb[names[0]]._sparse4 = out + (tuple(shape),)
+        cb[names[0]]._sparse4 = out + (tuple(shape), tuple(cb[c] for c in names))
         return out
 
     def _cellp(self, c: Coef):

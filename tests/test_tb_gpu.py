@@ -1,5 +1,6 @@
 """Temporally blocked kernel (yee3d_tb.hip) vs the torch fp64 oracle and vs
-repeated single fused steps on the GPU."""
+repeated single fused steps on the GPU.  (One launch on live, impedance-scaled
+state with sentinel outputs: tests/test_tb_plain_gpu.py and tests/test_tb_plain_cpu.py.)"""
 import dataclasses
 
 import pytest

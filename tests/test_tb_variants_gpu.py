@@ -98,7 +98,8 @@ DT = {"f32": torch.float32, "f64": torch.float64}
 
 # family -> (ROWS, LANES): see the module docstring
 GEOM = {"mr16x2": (32, 64), "mr8x4": (32, 64), "drude32": (16, 64), "f64half": (32, 32), "f64full": (16, 64),
-        "drude64": (16, 32)}
+        "drude64": (16, 32),
+        "mr8x2": (16, 64)}  # fp32 multi-row, 8 waves x 2 rows (tb_mr_shape 2, T <= 5: tests/test_tb_plain_gpu.py)
 
 
 def cdiv(a, b):
@@ -118,6 +119,12 @@ def tiles(family, T, obox, xchunk=XCHUNK):
 
 def seams(family, T, obox, xchunk=XCHUNK):
     """Interior tile / chunk boundaries of the launch along x, y, z."""
+    if family == "single":
+        # (16-row tiles of V wide lanes from ``O.lo.z`` rounded down to V: see ``tiles``)
+        V = 4 if T <= 2 else 2
+        step = (xchunk, 16 - 2 * T, (64 - 2 * cdiv(T, V)) * V)
+        lo = (obox[0][0], obox[0][1], obox[0][2] & ~(V - 1))
+        return [list(range(lo[d] + step[d], obox[1][d], step[d])) for d in range(3)]
     rows, lanes = GEOM[family]
     step = (xchunk, rows - 2 * T, lanes - 2 * T)
     return [list(range(obox[0][d] + step[d], obox[1][d], step[d])) for d in range(3)]
