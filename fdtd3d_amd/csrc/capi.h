@@ -259,6 +259,18 @@ int fdtd_probe_sample_f32(const void* tab, int nslots, void* series, int row, in
 int fdtd_probe_sample_f64(const void* tab, int nslots, void* series, int row, int capacity, void* s);
 int fdtd_probe_ent_size();
 
+// one half step of a source list (source_kernels.hip): tab = n device entries
+// of fdtd_source_ent_size() bytes (field array, element offset, fp64
+// amplitude, signal index, flags: 1 = same cell as the previous entry, 2 =
+// hard) sorted by cell, values = nvalues host doubles, the signals' values at
+// this half step.  hipErrorInvalidValue for nvalues outside [0,
+// fdtd_source_max_signals()], a negative n or a null pointer; n == 0 launches
+// nothing
+int fdtd_source_inject_f32(const void* tab, int n, const double* values, int nvalues, void* s);
+int fdtd_source_inject_f64(const void* tab, int n, const double* values, int nvalues, void* s);
+int fdtd_source_ent_size();
+int fdtd_source_max_signals();
+
 // file scenes (scene_kernels.hip): the magnetic Drude plasma frequency and the
 // collision frequencies of a component.  tab, points, origin, shape, stride,
 // mod, cull, out as fdtd_scene_sample; quantity 2 = omega_m, 3 = gamma, 4 =

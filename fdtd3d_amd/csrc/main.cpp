@@ -107,6 +107,7 @@ int main(int argc, char** argv) {
                  "the energy monitor and its decay-based stop (--use-energy, --stop-decay-by), "
                  "field probes (--use-probes), "
                  "file scenes (--scene file), "
+                 "source lists (--source-file), "
                  "and complex fields with amplitude mode, "
                  "NTFF, checkpoints or parallel grids run through the Python driver: python -m fdtd3d_amd <same options>\n");
     return 2;

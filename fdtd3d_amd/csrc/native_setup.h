@@ -650,6 +650,8 @@ bool native_supported(const fdtd::Settings& s) {
     return false;
   // file scenes (layout/scene_file.py, the scene_sample op) too
   if (s.scene == "file" || !s.sceneFile.empty()) return false;
+  // source lists (layout/source_file.py, the source_inject op) too
+  if (!s.sourceFile.empty()) return false;
   return !((s.doUsePML && !cpml_ok && !upml_ok) || (s.doUseTFSF && !tfsf_ok) || !meta_ok || !ntff_ok || !amp_ok ||
            !par_ok || !ckpt_ok || s.doUseDoubleMaterialPrecision ||
            // complex fields: two real planes of one-GPU runs (main.cpp run)

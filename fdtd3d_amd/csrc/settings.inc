@@ -191,5 +191,7 @@ FDTD_INT (probeStep, "--probe-step", 0, "Steps between probe samples; 0 = automa
 FDTD_INT (probeStart, "--probe-start", 0, "First step at which the probes sample")
 FDTD_INT (probeSpectrum, "--probe-spectrum", 0, "Report the spectrum of the probe series at this many wavelengths, evenly spaced in frequency over --probe-band (with --source gaussian divided by the source signal's spectrum); 0 = none")
 FDTD_STRING (probeBand, "--probe-band", "", "Band of --probe-spectrum as free-space wavelengths lo,hi (m)")
+/* ---- extensions: source files, soft and hard dipole sources at chosen cells (layout/source_file.py; Python driver) ---- */
+FDTD_STRING (sourceFile, "--source-file", "", "JSON file with a list of sources that replaces the built-in point source: per entry a component, the cell of its Yee sample, soft (added) or hard (set), an amplitude and a sine, gaussian or pulse signal; 2D and 3D")
 FDTD_BOOL (doPrintJson, "--json", "Print a JSON summary line after the run")
 FDTD_INT (warmupSteps, "--warmup-steps", 0, "Untimed time steps run before the timed loop (benchmarking; they advance the simulation)")

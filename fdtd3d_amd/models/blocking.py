@@ -198,7 +198,8 @@ class BlockedStepping:
             return None
         if (self.planes != 1 or cfg.use_amp_mode or self.graph_mode
                 or not self.use_upml_chain or getattr(self, "chain_regions", None) is None or self.use_cpml
-                or getattr(cfg, "dispersion", "drude") != "drude" or self.hooks):
+                or getattr(cfg, "dispersion", "drude") != "drude" or self.hooks
+                or getattr(self, "source_list", None) is not None):  # (a source list: the stepped dispersive box)
             return None
         if any("D1" in self.upml[c] for c in self.h_comps) or not any("D1" in self.upml[c] for c in self.e_comps):
             return None
@@ -466,6 +467,10 @@ class BlockedStepping:
                 if self.halo is not None:
                     H = self.domain.buffer_size  # decomposed: one pass per ghost exchange, every rank alike
         hmax = getattr(self.ops, "tb2d_max_steps" if two_d else "tb_max_steps", 8 if two_d else 6)
+        # a source list (layout/source_file.py): the blocked kernels know one hard point only, so such runs
+        # keep blocked throughput through a hybrid plan whose stepped windows cover the sources -- with or
+        # without absorbing layers
+        sources = getattr(self, "source_list", None) is not None
         dg = self._drude_glob
         if dg is not None and not self.fused and self.tb == 1 and dg[0] <= hmax:
             if not (cfg.use_pml or cfg.use_tfsf):
@@ -477,8 +482,10 @@ class BlockedStepping:
             H = dg[0]
         if (H <= 1 or self.fused or self.tb > 1 or cfg.scheme not in ("3d", "tmz", "tez")
                 or not hasattr(self.ops, "tb_step") or cfg.use_amp_mode or self.graph_mode
-                or not (cfg.use_pml or cfg.use_tfsf or cfg.use_metamaterials) or H > hmax):
+                or not (cfg.use_pml or cfg.use_tfsf or cfg.use_metamaterials or sources) or H > hmax):
             return
+        if sources and self.halo is not None:
+            return  # decomposed runs with a source list: the stepped / deep-halo path
         if self.halo is not None and (cfg.scheme != "3d" or self.domain.buffer_size != H):
             # decomposed: one T-deep exchange per pass feeds both the core and
             # the deep-halo stepped shell, so the ghosts must be exactly T deep
@@ -612,6 +619,11 @@ class BlockedStepping:
                 b = self._bbox_global(self.upml[c].get("drude_active"))
                 if not box_empty(b):
                     disp.append(b)
+        # so is the bounding box of a source list's cells: the stepped windows cover the sources, the core
+        # stays at least T + 1 cells clear of them
+        sbox = self.source_list.bbox() if getattr(self, "source_list", None) is not None else None
+        if sbox is not None:
+            disp.append(sbox)
         D = None
         for b in disp:
             D = b if D is None else (tuple(min(D[0][d], b[0][d]) for d in range(3)),
@@ -632,7 +644,7 @@ class BlockedStepping:
         if core_cells < 0.25 * size[0] * size[1] * size[2]:
             return None
         # verify: no irregular cell within T + 1 of an output box
-        irregular = []
+        irregular = [sbox] if sbox is not None else []
         if getattr(self, "chain_regions", None) is not None:
             for kind in ("E", "H"):
                 for r, _ in self.chain_regions[kind]["chain"]:

@@ -87,7 +87,28 @@ def auto_step(scheme) -> int:
 def source_end(scheme, budget: int) -> Optional[int]:
     """``t_src``: the first step from which ``|source_value(t, 0)|`` stays
     below ``SOURCE_OFF`` of its peak up to step ``budget``; None where the
-    source is still on at the end of the budget."""
+    source is still on at the end of the budget.  With a source list: the
+    latest end of all its signals, each against its own peak (None when one
+    of them is a sine)."""
+    sl = getattr(scheme, "source_list", None)
+    if sl is not None:
+        from ..layout.source_file import signal_value
+        if sl.has_sine():
+            return None
+        n = max(1, int(budget)) + 1
+        end = 0
+        for sig in sl.signals:
+            # both sample times of a step: E entries take tau = t, H entries t + 1/2
+            v = torch.tensor([max(abs(signal_value(sig, t, scheme.dt)), abs(signal_value(sig, t + 0.5, scheme.dt)))
+                              for t in range(n)], dtype=torch.float64)
+            peak = float(v.max())
+            if not peak > 0:
+                continue
+            last = int(torch.nonzero(v >= SOURCE_OFF * peak).flatten()[-1])
+            if last >= n - 1:
+                return None
+            end = max(end, last + 1)
+        return end
     v = scheme.source_values(0, max(1, int(budget)) + 1, 0).abs()
     peak = float(v.max())
     if not peak > 0:
@@ -108,6 +129,18 @@ def refuse_energy_config(cfg, checkpoints: bool = False) -> Optional[str]:
         return why
     if not 0.0 <= cfg.stop_decay_by < 1.0:
         return "--stop-decay-by: a fraction of the peak energy, 0 <= r < 1 (got %g)" % cfg.stop_decay_by
+    if cfg.stop_decay_by > 0 and getattr(cfg, "sources", None):
+        # a source list: every entry must end (layout/source_file.py; a malformed list is refused by its loader)
+        from ..layout.source_file import parse_sources
+        try:
+            entries = parse_sources(cfg.sources, cfg.scheme, cfg.wavelength, cfg.gaussian_width, cfg.gaussian_delay,
+                                    cfg.source)
+        except ValueError as e:
+            return str(e)
+        if any(e.signal.waveform == "sine" for e in entries):
+            return ("--stop-decay-by with a sine entry in the source list: that source never ends, so the field "
+                    "energy never decays; use the pulse or gaussian waveform")
+        return None
     if cfg.stop_decay_by > 0 and cfg.source != "gaussian":
         return ("--stop-decay-by with --source %s: the source never ends, so the field energy never decays; use "
                 "--source gaussian" % cfg.source)
@@ -160,7 +193,12 @@ class EnergyMonitor:
         self.t_src: Optional[int] = None
         if decay_by > 0:
             self.t_src = source_end(scheme, cfg.time_steps)
-            if cfg.source != "gaussian" or self.t_src is None:
+            listed = getattr(scheme, "source_list", None) is not None
+            if listed and self.t_src is None:
+                raise FdtdError("EnergyMonitor: decay_by needs sources that end within the %d time steps: an entry of "
+                                "the source list is a sine or a pulse still on at the last step, so the field energy "
+                                "would never decay" % cfg.time_steps)
+            if (cfg.source != "gaussian" and not listed) or self.t_src is None:
                 raise FdtdError("EnergyMonitor: decay_by needs a source that ends within the %d time steps (--source "
                                 "%s does not): the field energy would never decay" % (cfg.time_steps, cfg.source))
         dom = scheme.domain

@@ -147,6 +147,9 @@ class SchemeConfig:
     probe_start: int = 0
     probe_spectrum: int = 0                  # wavelengths of the reported spectrum, even in frequency; 0 = none
     probe_band: str = ""                     # "lo,hi" metres
+    sources: Optional[Sequence] = None       # a source list instead of the built-in point source: the entries of
+                                             # a source file as dicts (layout/source_file.py)
+    source_file: str = ""                    # the file ``sources`` was read from (messages only)
 
     @classmethod
     def from_settings(cls, s) -> "SchemeConfig":
@@ -171,7 +174,18 @@ class SchemeConfig:
                 check_scheme(scene_objects, scheme)
             except ValueError as e:
                 raise SettingsError("--scene-file %s: %s" % (s.sceneFile, e))
+        sources = None
+        if s.sourceFile:
+            # read once, here; the list is validated against the scheme and the grid by SourceList (refused
+            # before anything is set up: runner.run)
+            from ..layout.source_file import load_source_file
+            from ..utils.settings import SettingsError
+            try:
+                sources = load_source_file(s.sourceFile)
+            except ValueError as e:
+                raise SettingsError("--source-file %s: %s" % (s.sourceFile, e))
         return cls(
+            sources=sources, source_file=s.sourceFile,
             scheme=scheme, size=size, time_steps=s.numTimeSteps, amplitude_steps=s.numAmplitudeTimeSteps,
             pml_size=(s.pmlSizeX, s.pmlSizeY, s.pmlSizeZ), tfsf_size=(s.tfsfSizeX, s.tfsfSizeY, s.tfsfSizeZ),
             ntff_size=(s.ntffSizeX, s.ntffSizeY, s.ntffSizeZ), theta=s.incidentWaveAngle1,
@@ -254,6 +268,15 @@ class YeeScheme(BlockedStepping):
                                 math.radians(cfg.phi), math.radians(psi), cfg.double_material_precision)
         if ops.layout is None:
             ops.layout = self.layout
+        # a source list (layout/source_file.py) replaces the built-in point source; refused here, before
+        # anything is allocated
+        self.source_list = None
+        if cfg.sources:
+            from ..layout.source_file import SourceList
+            try:
+                self.source_list = SourceList(cfg, self.layout)
+            except ValueError as e:
+                raise FdtdError(str(e))
         self.comps = self.layout.components
         self.e_comps = tuple(c for c in self.comps if c[0] == "E")
         self.h_comps = tuple(c for c in self.comps if c[0] == "H")
@@ -383,13 +406,13 @@ class YeeScheme(BlockedStepping):
         # hard E point source
         self.fused = (cfg.use_fused and hasattr(self.ops, "fused_step") and cfg.scheme == "3d"
                       and not self.use_upml_chain and not self.use_cpml and not cfg.use_tfsf
-                      and not cfg.use_amp_mode)
+                      and not cfg.use_amp_mode and self.source_list is None)
         # plain 3D runs with TF/SF injection: the fp32 blocked kernel applies
         # the corrections itself (models/tfsf.py TfsfSets), so such serial runs
         # take blocked passes like plain ones (single steps keep the tables)
         self.tfsf_blocked = (cfg.use_tfsf and getattr(self, "tfsf_sets", None) is not None and cfg.use_fused
                              and cfg.scheme == "3d" and not self.use_upml_chain and not self.use_cpml
-                             and not cfg.use_amp_mode and self.halo is None)
+                             and not cfg.use_amp_mode and self.halo is None and self.source_list is None)
         if self.fused or self.tfsf_blocked:
             self.F_alt = [{c: self._zeros() for c in self.comps} for _ in range(self.planes)]
         # HIP graph mode (--use-hip-graph): serial HIP runs capture GRAPH_STEPS
@@ -430,7 +453,7 @@ class YeeScheme(BlockedStepping):
         # whole 16-byte lanes) or the generic oracle; F_alt is its ping-pong buffer
         if (cfg.scheme in ("tmz", "tez") and T > 1 and cfg.use_fused and hasattr(self.ops, "tb_step")
                 and not self.use_upml_chain and not self.use_cpml and not cfg.use_tfsf and not cfg.use_amp_mode
-                and not self.graph_mode
+                and not self.graph_mode and self.source_list is None
                 and (self.ops.name != "hip" or self.domain.shape[1] % (16 // self.dtype.itemsize) == 0)
                 and T <= getattr(self.ops, "tb2d_max_steps", 8)
                 and (self.halo is None or self.domain.buffer_size == T)):
@@ -1029,6 +1052,10 @@ class YeeScheme(BlockedStepping):
         size = cfg.size
         self.point_source = None
         self.line_source = None
+        self._src_entries = None
+        if self.source_list is not None:
+            self._init_source_list()
+            return
         if cfg.use_tfsf and not cfg.use_point_source:
             return
         if cfg.scheme == "3d":
@@ -1060,6 +1087,54 @@ class YeeScheme(BlockedStepping):
             li0 = self.domain.local_index((size[0] // 8, size[1] // 2, lo))
             if self.halo is None and li0 is not None and hi > lo:
                 self.line_box = ("Ez", li0[0], li0[1], li0[2], li0[2] + hi - lo)
+
+    def _init_source_list(self) -> None:
+        """This rank's entries of the source list (ops/source.py): one per
+        source cell its arrays hold, ghosts included -- the redundant steps of
+        a deep halo need them, and a one-deep ghost is overwritten by the
+        exchange that follows the injection.  A cell whose component is
+        advanced by the D/B chain (UPML slabs, a dispersive box) is refused:
+        there the field is recomputed from D every step.  Unlike the
+        refusals of ``SourceList`` this one needs the chain boxes, so it
+        comes during ``init_grids``."""
+        from ..ops.source import SourceEntries
+        sl = self.source_list
+        dim = {"3d": 3, "tmz": 2, "tez": 2}[self.cfg.scheme]
+        if self.use_upml_chain:
+            # (known only now: the chain boxes follow from the sampled materials and sigma profiles, so this
+            # one refusal comes at grid set-up, after the fields are allocated)
+            hint = " (--pml-type cpml keeps the absorbing layers out of the D/B chain)" if self.cfg.use_pml else ""
+            for c, g, _, _, _ in sl.cells:
+                for r, _ in self.chain_regions[c[0]]["chain"]:
+                    b = r.get(c)
+                    if b is not None and not box_empty(b) and all(b[0][d] <= g[d] < b[1][d] for d in range(3)):
+                        raise FdtdError("sources: %s at cell %s lies in a box advanced by the D/B chain (an absorbing "
+                                        "slab or a dispersive box), which recomputes the field from D every step%s"
+                                        % (c, g[:dim], hint))
+        ent = SourceEntries()
+        for c in self.comps:  # array n of the entries = component n
+            ent.add_field(self.F[0][c])
+        shape = tuple(self.domain.shape)
+        rows = {"E": [], "H": []}
+        for c, g, amp, sig, hard in sl.cells:
+            li = self.domain.local_index(g)
+            if li is not None:
+                rows[c[0]].append((self.comps.index(c), (li[0] * shape[1] + li[1]) * shape[2] + li[2], amp, sig, hard))
+        for kind in ("E", "H"):
+            rows[kind].sort(key=lambda r: (r[0], r[1]))  # by cell; a cell's entries keep the file's order
+            ent.rows[kind] = rows[kind]
+        self._src_entries = ent
+
+    def _inject_sources(self, kind: str, t: int) -> None:
+        """The source list's entries of ``kind`` after that half step's
+        update: one backend op (HIP: one launch), the signals' values at ``tau
+        = t`` (E) / ``t + 1/2`` (H) evaluated on the host in fp64."""
+        ent = self._src_entries
+        if ent is None or not ent.rows[kind]:
+            return
+        for i, c in enumerate(self.comps):
+            ent.fields[i] = self.F[0][c]  # the current array: F / F_alt ping-pong
+        self.ops.source_inject(ent, kind, self.source_list.values(t if kind == "E" else t + 0.5, self.dt))
 
     def source_value(self, t: int, plane: int) -> float:
         cfg = self.cfg
@@ -1531,6 +1606,9 @@ class YeeScheme(BlockedStepping):
         return out
 
     def _apply_sources(self, t: int, p: int) -> None:
+        if self.source_list is not None:
+            self._inject_sources("E", t)
+            return
         if self.line_source is not None and self.cfg.use_amp_mode and self.in_amplitude:
             comp, offs = self.line_source
             if offs.numel():
@@ -1595,6 +1673,9 @@ class YeeScheme(BlockedStepping):
                     halo.finish_and_update(self, "H", p)
                 else:
                     self._update("H", p, windows, tfsf_once=windows is not None and self._tfsf_once)
+            if self.source_list is not None:
+                with ph("source"):
+                    self._inject_sources("H", t)
             if halo is not None and not deep:
                 with ph("halo-post"):
                     halo.start(self, "H", p)
@@ -1795,6 +1876,8 @@ class YeeScheme(BlockedStepping):
                 or not hasattr(self.ops, "inc_step_e_tab") or not hasattr(self.ops, "counter_add")
                 or getattr(self.cfg, "hybrid_graph", "auto") == "off"):
             return 0
+        if self.source_list is not None:
+            return 0  # planned every pass: a record or graph would replay stale by-value signal values
         if self.point_source is not None and self.point_source[1] is not None:
             li = self.point_source[1]
             if any(all(b[0][d] <= li[d] < b[1][d] for d in range(3)) for b in hp["core"]):

@@ -1,7 +1,7 @@
 """The monitor operations of the HIP backend, a mixin of
 :class:`~.hip_ops.HipOps`: ``dft_accumulate``, ``dft_flux``, ``dft_farfield``,
-``field_sumsq`` and ``probe_sample`` (csrc/dft_, flux_, farfield_, energy_,
-probe_kernels.hip).  Each
+``field_sumsq``, ``probe_sample`` and ``source_inject`` (csrc/dft_, flux_,
+farfield_, energy_, probe_, source_kernels.hip).  Each
 runs from a device table of fixed-size entries, built once per monitor (and
 set of arrays) and cached on its entries / terms; the builders validate all
 the kernels rely on, which check nothing beyond their boxes.
@@ -448,4 +448,66 @@ class HipMonitorOps:
         rc = self.fn("probe_sample")(_ptr(tab), c_int(len(entries)), _ptr(series), c_int(row),
                                      c_int(entries.capacity), _stream())
         _check(rc, "probe_sample")
+        self.launches += 1
+
+    # ------------------------------------------------------------ source lists
+    def _source_table(self, entries, kind: str):
+        """The device table of a source list's entries of ``kind`` with their
+        current field arrays (rows sorted by cell, ops/source.py)."""
+        from .source import FLAG_HARD, FLAG_SAME, SOURCE_ENT_SIZE, SOURCE_MAX_SIGNALS
+        self._check_ent_size("Src", "source", SOURCE_ENT_SIZE)
+        if int(self.lib.raw.fdtd_source_max_signals()) != SOURCE_MAX_SIGNALS:
+            raise HipError("SrcEnt layout mismatch")
+        rows = entries.rows[kind]
+        item = 16 // vec_width(self.dtype)
+        for fi in sorted({r[0] for r in rows}):
+            f = entries.fields[fi]
+            self._check_tensor(f)
+            if f.data_ptr() % item:
+                raise HipError("source_inject: field array not aligned to its element size")
+        if len(rows) >= 2 ** 31 - 256:
+            raise HipError("source_inject: too many entries for one launch")
+        e64, e32, ef = _ent_table(len(rows), SOURCE_ENT_SIZE)
+        prev = None
+        for n, (fi, off, amp, sig, hard) in enumerate(rows):
+            e64[n, 0] = entries.fields[fi].data_ptr()
+            e64[n, 1] = off
+            ef[n, 2] = amp
+            e32[n, 6] = sig
+            e32[n, 7] = (FLAG_SAME if (fi, off) == prev else 0) | (FLAG_HARD if hard else 0)
+            prev = (fi, off)
+        return torch.from_numpy(e64).to(self.device)
+
+    def source_inject(self, entries, kind: str, values) -> None:
+        """One half step of a source list (ops/source.py ``SourceEntries``)
+        in ONE launch over all its entries of ``kind`` (source_kernels.hip
+        k_source_inject), ``values`` (the signals' fp64 values at this half
+        step) passed by value.  Every offset and signal index is validated
+        when the device table is built; the table, its length and the signal
+        count it needs are cached on ``entries`` per kind and set of field
+        arrays (F / F_alt ping-pong), so a launch checks the value count only
+        -- nothing per launch grows with the list."""
+        try:
+            key = entries.key(kind)
+        except ValueError as e:
+            raise HipError("source_inject: %s" % e)
+        cached = entries.tables.get(key)
+        if cached is None:
+            why = entries.table_error(kind)
+            if why:
+                raise HipError("source_inject: " + why)
+            rows = entries.rows[kind]
+            cached = (self._source_table(entries, kind) if rows else None, len(rows), entries.signals_needed(kind))
+            if len(entries.tables) >= 2 * self.PROBE_MAX_TABLES:
+                entries.tables.clear()  # reallocated field arrays: drop the tables of the old ones
+            entries.tables[key] = cached
+        tab, nrows, needed = cached
+        why = entries.values_error(len(values), needed)
+        if why:
+            raise HipError("source_inject: " + why)
+        if not nrows:
+            return
+        vals = (c_double * len(values))(*values)
+        rc = self.fn("source_inject")(_ptr(tab), c_int(nrows), vals, c_int(len(values)), _stream())
+        _check(rc, "source_inject")
         self.launches += 1

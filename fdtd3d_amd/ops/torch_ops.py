@@ -686,6 +686,66 @@ class TorchOps:
                 raise ValueError("probe_sample: contiguous field arrays")
             series[int(row), cols] = f.reshape(-1)[offs].double()
 
+    def source_inject(self, entries, kind: str, values) -> None:
+        """One half step of a source list (ops/source.py ``SourceEntries``):
+        every distinct cell of the entries of ``kind`` becomes its value
+        widened to fp64 (0 when the cell's first entry is hard) plus
+        ``amplitude * values[signal]`` for each of its entries in table order
+        -- product and sum rounded separately --, rounded once to the field
+        type.  The oracle of csrc/source_kernels.hip, bit for bit."""
+        values = [float(v) for v in values]
+        key = ("torch",) + entries.key(kind)
+        cached = entries.tables.get(key)  # offsets and signal indices are checked once per plan
+        if cached is None:
+            why = entries.table_error(kind)
+            if why:
+                raise ValueError("source_inject: " + why)
+        why = entries.values_error(len(values), entries.signals_needed(kind) if cached is None else cached[1])
+        if why:
+            raise ValueError("source_inject: " + why)
+        rows = entries.rows[kind]
+        if not rows:
+            return
+        plan = None if cached is None else cached[0]  # per array: its cells and, per round, the k-th entries
+        if plan is None:
+            plan = []
+            for fi in sorted({r[0] for r in rows}):
+                dev = entries.fields[fi].device
+                offs, hard, rounds = [], [], []
+                for (i, off, amp, sig, hd) in rows:
+                    if i != fi:
+                        continue
+                    if not offs or offs[-1] != off:
+                        offs.append(off)
+                        hard.append(hd)
+                        k = 0
+                    else:
+                        k += 1
+                    while len(rounds) <= k:
+                        rounds.append(([], [], []))
+                    rounds[k][0].append(len(offs) - 1)
+                    rounds[k][1].append(amp)
+                    rounds[k][2].append(sig)
+                plan.append((fi, torch.tensor(offs, dtype=torch.int64, device=dev),
+                             torch.tensor(hard, dtype=torch.bool, device=dev),
+                             [(torch.tensor(c, dtype=torch.int64, device=dev),
+                               torch.tensor(a, dtype=torch.float64, device=dev),
+                               torch.tensor(s, dtype=torch.int64, device=dev)) for c, a, s in rounds]))
+            if len(entries.tables) >= 8:
+                entries.tables.clear()
+            entries.tables[key] = (plan, entries.signals_needed(kind))
+        for fi, offs, hard, rounds in plan:
+            f = entries.fields[fi]
+            if not f.is_contiguous():
+                raise ValueError("source_inject: contiguous field arrays")
+            flat = f.reshape(-1)
+            vals = torch.tensor(values, dtype=torch.float64, device=f.device)
+            acc = torch.where(hard, torch.zeros((), dtype=torch.float64, device=f.device), flat[offs].double())
+            for cells, amp, sig in rounds:
+                term = amp * vals[sig]
+                acc[cells] = acc[cells] + term
+            flat[offs] = acc.to(f.dtype)
+
     def scene_sample(self, table, quantity: str, points, origin, shape, stride, mod, out=None) -> torch.Tensor:
         """A file scene (layout/scene_file.py ``SceneTable``) evaluated and
         averaged onto one component: fp64 tensor of ``shape``.  Cell ``i`` takes

@@ -63,15 +63,16 @@ def _init_distributed(settings: Settings):
     return dist, dist.get_rank(), dist.get_world_size()
 
 
-def build(settings: Settings, rank: int = 0, world: int = 1):
-    """Create (scheme, halo, core) for the settings on this rank."""
+def build(settings: Settings, rank: int = 0, world: int = 1, cfg=None):
+    """Create (scheme, halo, core) for the settings on this rank (``cfg``:
+    their configuration where the caller has built it already)."""
     import torch
     from .models.scheme import SchemeConfig, YeeScheme
     from .ops import make_ops, resolve_backend
     from .parallel.halo import HaloExchanger
     from .parallel.topology import ParallelGridCore, read_available_topologies
 
-    cfg = SchemeConfig.from_settings(settings)
+    cfg = SchemeConfig.from_settings(settings) if cfg is None else cfg
     backend, device = resolve_backend(settings.backend, settings.device)
     if device.startswith("cuda"):
         local = int(os.environ.get("LOCAL_RANK", rank))
@@ -163,6 +164,26 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
     if status != EXIT_OK:
         return status
     log.set_level(settings.logLevel)
+    # the configuration is built once, here: the scene and source files are read and refused before anything
+    # is set up (layout/scene_file.py, layout/source_file.py)
+    from .models.scheme import SchemeConfig
+    from .utils.settings import SettingsError
+    try:
+        cfg0 = SchemeConfig.from_settings(settings)
+    except SettingsError as e:
+        out.write("ERROR: %s\n" % e)
+        return EXIT_ERROR
+    ckpt = bool(settings.checkpointDir or settings.loadFromFile)
+    if cfg0.sources:
+        from .layout.source_file import SourceList, refuse_source_config
+        try:
+            why = refuse_source_config(cfg0, checkpoints=ckpt)
+            if why:
+                raise ValueError(why)
+            SourceList(cfg0)
+        except ValueError as e:
+            out.write("ERROR: %s\n" % e)
+            return EXIT_ERROR
     if (settings.doUseDft or settings.doUseNtffDft or settings.doUseFlux or settings.doUseFarfield
             or settings.doUseEnergy or settings.stopDecayBy != 0 or settings.doUseProbes):
         # refused before anything is set up, never a silent fallback (models/dft.py, models/energy.py,
@@ -170,22 +191,10 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         from .models.dft import refuse_config
         from .models.energy import refuse_energy_config
         from .models.probe import refuse_probe_config
-        from .models.scheme import SchemeConfig
-        cfg0 = SchemeConfig.from_settings(settings)
-        ckpt = bool(settings.checkpointDir or settings.loadFromFile)
         why = (refuse_config(cfg0, checkpoints=ckpt) or refuse_energy_config(cfg0, checkpoints=ckpt)
                or refuse_probe_config(cfg0, checkpoints=ckpt))
         if why:
             out.write("ERROR: %s\n" % why)
-            return EXIT_ERROR
-    if settings.scene == "file":
-        # the scene file is read and refused here, before anything is set up
-        from .models.scheme import SchemeConfig
-        from .utils.settings import SettingsError
-        try:
-            SchemeConfig.from_settings(settings)
-        except SettingsError as e:
-            out.write("ERROR: %s\n" % e)
             return EXIT_ERROR
     dist, rank, world = _init_distributed(settings)
     log.set_rank(rank)
@@ -194,7 +203,7 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
     from .io.dump import dump_fields, dump_materials
     from .models.ntff import ntff_report
 
-    scheme, halo, core = build(settings, rank, world)
+    scheme, halo, core = build(settings, rank, world, cfg0)
     scheme.init_scheme()
     scheme.init_grids()
     log.info("scheme %s size %s backend %s dtype %s" % (scheme.cfg.scheme, scheme.cfg.size, scheme.ops.name,
@@ -358,7 +367,8 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         series = probes.series()
         if series is not None:
             spec, wl = None, []
-            pulsed = scheme.cfg.source == "gaussian"  # a spectrum of the system: divided by the pulse's
+            # a spectrum of the system: divided by the pulse's (a source list has no one signal to divide by)
+            pulsed = scheme.cfg.source == "gaussian" and scheme.source_list is None
             if scheme.cfg.probe_spectrum > 0 and probes.samples:
                 wl = band_wavelengths(scheme.cfg.probe_spectrum, scheme.cfg.probe_band)
                 spec = probes.spectrum(wl, normalise=pulsed, series=series)
@@ -404,6 +414,8 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                 rec["energy"] = energy.info(energy_result)
             if probes_info is not None:
                 rec["probes"] = probes_info
+            if scheme.source_list is not None:
+                rec["sources"] = scheme.source_list.info()
             if scheme.cfg.scene == "file":
                 rec["scene"] = {"objects": len(scheme.scene.objects)}
                 triangles = sum(len(o.mesh) for o in scheme.scene.objects if o.mesh is not None)
