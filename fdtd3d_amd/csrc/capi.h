@@ -286,4 +286,26 @@ int fdtd_scene_sample_drude_mesh(const void* tab, int nobj, int quantity, const 
                                  void* out, void* s, const void* drude, int ndrude, const void* tris, int ntris,
                                  const void* ranges);
 int fdtd_scene_drude_size();
+
+// file scenes (scene_kernels.hip): the conductivity of a component (the scene-file key sigma), painted by
+// the rule of eps over 0.  Arguments as fdtd_scene_sample; quantity 5; cond = ncond (== nobj) device doubles,
+// S/m.  hipErrorInvalidValue, with nothing launched, for a null pointer, another quantity or ncond != nobj
+int fdtd_scene_sample_cond(const void* tab, int nobj, int quantity, const int* points, int npts, const int* origin,
+                           const int* shape, const int* stride, double mod, int cull, void* out, void* s,
+                           const void* cond, int ncond);
+int fdtd_scene_sample_cond_mesh(const void* tab, int nobj, int quantity, const int* points, int npts,
+                                const int* origin, const int* shape, const int* stride, double mod, int cull,
+                                void* out, void* s, const void* cond, int ncond, const void* tris, int ntris,
+                                const void* ranges);
+
+// the conductive E update of a lossy box (lossy_kernels.hip): E = ca * E + cb * curl(H) on the three boxes
+// (boxes = Ex, Ey, Ez as 6 ints each, local indices) in one launch.  e / h = the three field arrays of
+// shape (nx, ny, nz); ca / cb = the three coefficient arrays each, stored over rbox (6 ints, local indices).
+// hipErrorInvalidValue, with nothing launched, for a null pointer, a box outside the arrays or rbox, or a box
+// whose curl would read index -1.  lanes (may be null) receives the cells a lane owns: 16 bytes' worth when nz
+// and rbox's z range are whole lanes and every array is 16-byte aligned, else 1
+int fdtd_lossy_e_f32(void* const* e, const void* const* h, const void* const* ca, const void* const* cb, int nx,
+                     int ny, int nz, const int* boxes, const int* rbox, void* s, int* lanes);
+int fdtd_lossy_e_f64(void* const* e, const void* const* h, const void* const* ca, const void* const* cb, int nx,
+                     int ny, int nz, const int* boxes, const int* rbox, void* s, int* lanes);
 }

@@ -5,6 +5,8 @@
 // SCENE_WITH_DRUDE 1 (k_scene_sample_drude and its mesh twin, Q = 2 omega_m, 3 gamma, 4 gamma_m; the
 // parameter drude in scope) compiles in the second table and, for a collision frequency, the damping g painted
 // beside the pole v; with 0 the preprocessor drops those statements too, and eps / omega stay what they were.
+// SCENE_WITH_COND 1 (k_scene_sample_cond and its mesh twin, Q = 5; the parameter cond in scope, one double per
+// object) paints the conductivity by the rule of eps, over 0; with 0 every such test folds away.
 #pragma clang fp contract(off)
 constexpr bool MESH = SCENE_WITH_MESH;
   const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
@@ -75,6 +77,8 @@ constexpr bool MESH = SCENE_WITH_MESH;
     // dispersive) and the damping that goes with it
     const double obj = Q == 3 ? E[o].omega : D[o].omega_m;
     const double damp = Q == 3 ? D[o].gamma_e : D[o].gamma_m;
+#elif SCENE_WITH_COND
+    const double obj = ((mon::ConstTab<double>)cond)[o];
 #else
     const double obj = Q == 0 ? E[o].eps : E[o].omega;
 #endif
@@ -82,7 +86,7 @@ constexpr bool MESH = SCENE_WITH_MESH;
     // a mesh: bit 8 j + k of par = the parity of the triangles crossed above point (j, k), dm = the
     // squared distance of the closest one (under linear smoothing)
     const bool is_mesh = kind == SCENE_MESH;
-    const bool magnitude = Q == 0 && !(flags & SCENE_SHARP);
+    const bool magnitude = (Q == 0 || SCENE_WITH_COND) && !(flags & SCENE_SHARP);
     unsigned par = 0u;
     double dm[2][SCENE_MAX_POINTS];
     if (is_mesh) {
@@ -158,7 +162,7 @@ constexpr bool MESH = SCENE_WITH_MESH;
         const double d = scene_dist(kind, flags, a, b, P);
 #endif
         const double below = v[j][k];
-        if (Q >= 1 || (flags & SCENE_SHARP)) {
+        if ((Q >= 1 && !SCENE_WITH_COND) || (flags & SCENE_SHARP)) {
           v[j][k] = d < 0.0 ? obj : below;
 #if SCENE_WITH_DRUDE
           if (Q >= 3) g[j][k] = d < 0.0 ? damp : g[j][k];
@@ -175,7 +179,7 @@ constexpr bool MESH = SCENE_WITH_MESH;
   double res[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    if (Q == 0) {
+    if (Q == 0 || SCENE_WITH_COND) {
       // the pairwise-hierarchical mean (layout/approximation.py approximate_material)
       double m[SCENE_MAX_POINTS];
 #pragma unroll

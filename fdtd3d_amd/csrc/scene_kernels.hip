@@ -201,7 +201,9 @@ __global__ __launch_bounds__(256) void k_scene_sample(const SceneEnt* __restrict
                                                       SceneArgs A) {
 #define SCENE_WITH_MESH 0
 #define SCENE_WITH_DRUDE 0
+#define SCENE_WITH_COND 0
 #include "scene_body.inc"
+#undef SCENE_WITH_COND
 #undef SCENE_WITH_DRUDE
 #undef SCENE_WITH_MESH
 }
@@ -211,7 +213,9 @@ __global__ __launch_bounds__(256) void k_scene_sample_mesh(const SceneEnt* __res
                                                            double* __restrict__ out, SceneArgs A, SceneMesh M) {
 #define SCENE_WITH_MESH 1
 #define SCENE_WITH_DRUDE 0
+#define SCENE_WITH_COND 0
 #include "scene_body.inc"
+#undef SCENE_WITH_COND
 #undef SCENE_WITH_DRUDE
 #undef SCENE_WITH_MESH
 }
@@ -222,7 +226,9 @@ __global__ __launch_bounds__(256) void k_scene_sample_drude(const SceneEnt* __re
                                                             double* __restrict__ out, SceneArgs A) {
 #define SCENE_WITH_MESH 0
 #define SCENE_WITH_DRUDE 1
+#define SCENE_WITH_COND 0
 #include "scene_body.inc"
+#undef SCENE_WITH_COND
 #undef SCENE_WITH_DRUDE
 #undef SCENE_WITH_MESH
 }
@@ -233,7 +239,35 @@ __global__ __launch_bounds__(256) void k_scene_sample_drude_mesh(const SceneEnt*
                                                                  double* __restrict__ out, SceneArgs A, SceneMesh M) {
 #define SCENE_WITH_MESH 1
 #define SCENE_WITH_DRUDE 1
+#define SCENE_WITH_COND 0
 #include "scene_body.inc"
+#undef SCENE_WITH_COND
+#undef SCENE_WITH_DRUDE
+#undef SCENE_WITH_MESH
+}
+
+template <int Q>  // 5: cond
+__global__ __launch_bounds__(256) void k_scene_sample_cond(const SceneEnt* __restrict__ tab,
+                                                           const double* __restrict__ cond,
+                                                           double* __restrict__ out, SceneArgs A) {
+#define SCENE_WITH_MESH 0
+#define SCENE_WITH_DRUDE 0
+#define SCENE_WITH_COND 1
+#include "scene_body.inc"
+#undef SCENE_WITH_COND
+#undef SCENE_WITH_DRUDE
+#undef SCENE_WITH_MESH
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void k_scene_sample_cond_mesh(const SceneEnt* __restrict__ tab,
+                                                                const double* __restrict__ cond,
+                                                                double* __restrict__ out, SceneArgs A, SceneMesh M) {
+#define SCENE_WITH_MESH 1
+#define SCENE_WITH_DRUDE 0
+#define SCENE_WITH_COND 1
+#include "scene_body.inc"
+#undef SCENE_WITH_COND
 #undef SCENE_WITH_DRUDE
 #undef SCENE_WITH_MESH
 }
@@ -366,6 +400,35 @@ FDTD_API int fdtd_scene_sample_drude_mesh(const void* tab, int nobj, int quantit
     k_scene_sample_drude_mesh<3><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A, M);
   else
     k_scene_sample_drude_mesh<4><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A, M);
+  FDTD_RETURN_LAUNCH_STATUS();
+}
+// The conductivity: quantity 5, `cond` = ncond device doubles, one per object (ncond == nobj, S/m);
+// everything else as fdtd_scene_sample.
+FDTD_API int fdtd_scene_sample_cond(const void* tab, int nobj, int quantity, const int* points, int npts,
+                                    const int* origin, const int* shape, const int* stride, double mod, int cull,
+                                    void* out, void* s, const void* cond, int ncond) {
+  if (!cond || ncond != nobj) return (int)hipErrorInvalidValue;
+  SceneArgs A;
+  const int rc = scene_args(tab, nobj, quantity, 5, 5, points, npts, origin, shape, stride, mod, cull, out, A);
+  if (rc) return rc < 0 ? 0 : rc;
+  k_scene_sample_cond<5><<<cdiv(A.waves, 4), 256, 0, (hipStream_t)s>>>((const SceneEnt*)tab, (const double*)cond,
+                                                                       (double*)out, A);
+  FDTD_RETURN_LAUNCH_STATUS();
+}
+
+// The same for a scene with meshes: `tris`, `ntris`, `ranges` as fdtd_scene_sample_mesh.
+FDTD_API int fdtd_scene_sample_cond_mesh(const void* tab, int nobj, int quantity, const int* points, int npts,
+                                         const int* origin, const int* shape, const int* stride, double mod,
+                                         int cull, void* out, void* s, const void* cond, int ncond,
+                                         const void* tris, int ntris, const void* ranges) {
+  if (!cond || ncond != nobj) return (int)hipErrorInvalidValue;
+  if (ntris < 0 || ntris > SCENE_MAX_TRIANGLES || (ntris > 0 && !tris) || !ranges) return (int)hipErrorInvalidValue;
+  SceneArgs A;
+  const int rc = scene_args(tab, nobj, quantity, 5, 5, points, npts, origin, shape, stride, mod, cull, out, A);
+  if (rc) return rc < 0 ? 0 : rc;
+  const SceneMesh M = {(const SceneTri*)tris, (const SceneRange*)ranges, ntris};
+  k_scene_sample_cond_mesh<5><<<cdiv(A.waves, 4), 256, 0, (hipStream_t)s>>>((const SceneEnt*)tab,
+                                                                            (const double*)cond, (double*)out, A, M);
   FDTD_RETURN_LAUNCH_STATUS();
 }
 FDTD_API int fdtd_scene_drude_size() { return (int)sizeof(SceneDrude); }

@@ -200,15 +200,17 @@ def dump_dft(scheme, monitor, settings, step: int, directory: Optional[str] = No
 
 
 def dump_materials(scheme, settings, directory: Optional[str] = None) -> List[str]:
-    """Eps / Mu (and Drude omega/gamma with metamaterials) on the eps layout of
+    """Eps / Mu (and Drude omega/gamma with metamaterials, SigmaE with lossy media) on the eps layout of
     the local region (reference ``initGrids`` dumps)."""
     directory = directory or settings.outputDir
     rank = scheme.domain.rank
     names = ["eps", "mu"]
     if scheme.cfg.use_metamaterials:
         names += ["omega_pe", "gamma_e", "omega_pm", "gamma_m"]
+    if scheme.sampler.uniform("cond") != 0.0:
+        names.append("cond")  # a file scene with sigma: the conductivity, S/m
     labels = {"eps": "Eps", "mu": "Mu", "omega_pe": "OmegaPE", "gamma_e": "GammaE", "omega_pm": "OmegaPM",
-              "gamma_m": "GammaM"}
+              "gamma_m": "GammaM", "cond": "SigmaE"}
     files = []
     dim = {"3d": 3, "tmz": 2, "tez": 2, "1d": 1}[scheme.cfg.scheme]
     for n in names:

@@ -45,6 +45,9 @@ from .yee import MATERIAL_STENCIL, MATERIAL_STENCIL_DOUBLE, YeeLayout
 # a file scene's Drude materials: (scene_sample's quantity, the SceneObject field)
 _FILE_DRUDE = {"omega_pe": ("omega", "omega_p"), "gamma_e": ("gamma", "gamma"),
                "omega_pm": ("omega_m", "omega_pm"), "gamma_m": ("gamma_m", "gamma_m")}
+# a file scene's materials painted and averaged by the rule of eps: (scene_sample's quantity, the SceneObject
+# field, the value of vacuum); "cond" is the conductivity in S/m (the key sigma)
+_FILE_EPS_LIKE = {"eps": ("eps", "eps", 1.0), "cond": ("cond", "sigma", 0.0)}
 
 SQRT2_F32 = float(np.float32(np.sqrt(np.float32(2.0))))  # reference uses sqrtf(2.0)
 
@@ -134,8 +137,10 @@ class Scene:
         of evaluating and averaging a full fp64 grid (8 GB per array at
         1024^3)."""
         two_d_ref = self.kind == "reference" and self.scheme != "3d"
-        if self.kind == "file" and name == "eps":
-            return None if any(o.eps != 1.0 for o in self.objects) else 1.0
+        if name in _FILE_EPS_LIKE and (self.kind == "file" or name == "cond"):
+            _, field, vac = _FILE_EPS_LIKE[name]
+            objects = self.objects if self.kind == "file" else ()
+            return None if any(getattr(o, field) != vac for o in objects) else vac
         if self.kind == "file" and name in _FILE_DRUDE:
             return None if any(getattr(o, _FILE_DRUDE[name][1]) != 0.0 for o in self.objects) else 0.0
         if name == "eps":
@@ -216,7 +221,7 @@ class MaterialSampler:
     def grid(self, name: str) -> torch.Tensor:
         if name not in self._cache and self.scene.kind == "file":
             lo, shp = self._eps_region()
-            if name == "eps" or name in _FILE_DRUDE:
+            if name in _FILE_EPS_LIKE or name in _FILE_DRUDE:
                 self._cache[name] = self._sample(name, [(0, 0, 0)], lo, shp, (1, 1, 1))
             else:
                 self._cache[name] = torch.full(shp, 1.0 if name == "mu" else 0.0, dtype=self.dtype, device=self.device)
@@ -225,7 +230,7 @@ class MaterialSampler:
             x, y, z = self.scene._coords(lo, shp, self.mod, self.device, self.dtype)
             fn = {"eps": self.scene.eps, "mu": self.scene.mu, "omega_pe": self.scene.omega_pe,
                   "omega_pm": self.scene.omega_pm, "gamma_e": self.scene.gamma_e,
-                  "gamma_m": self.scene.gamma_m}[name]
+                  "gamma_m": self.scene.gamma_m, "cond": lambda x, y, z, mod: torch.zeros_like(x)}[name]
             self._cache[name] = fn(x, y, z, self.mod)
         return self._cache[name]
 
@@ -251,8 +256,8 @@ class MaterialSampler:
         if self.ops is None:
             from ..ops.torch_ops import TorchOps
             self.ops = TorchOps(self.layout, self.device, self.dtype)
-        return self.ops.scene_sample(self.scene.table(), "eps" if name == "eps" else _FILE_DRUDE[name][0], points,
-                                     origin, shape, stride, self.mod)
+        quantity = _FILE_EPS_LIKE[name][0] if name in _FILE_EPS_LIKE else _FILE_DRUDE[name][0]
+        return self.ops.scene_sample(self.scene.table(), quantity, points, origin, shape, stride, self.mod)
 
     def _stencil(self, comp: str):
         """(points, origin, stride) of component ``comp`` for ``scene_sample``:
@@ -273,10 +278,10 @@ class MaterialSampler:
         """Material ``name`` averaged at the positions of component ``comp``
         over the local allocated region (shape == local field shape)."""
         if self.scene.kind == "file":
-            if name != "eps":
+            if name not in _FILE_EPS_LIKE:
                 return torch.full(self.shape, 1.0 if name == "mu" else 0.0, dtype=self.dtype, device=self.device)
             pts, origin, stride = self._stencil(comp)
-            return self._sample("eps", pts, origin, self.shape, stride)
+            return self._sample(name, pts, origin, self.shape, stride)
         return approximate_material(self._points(comp, self.grid(name)))
 
     def averaged_drude(self, comp: str, electric: bool):

@@ -20,7 +20,11 @@ convention of ``--sphere-center-*``).  ``eps`` is the relative permittivity
 the plasma and collision frequencies of a magnetic Drude pole (the same units,
 default 0, sharp like ``omega_p``); a damping needs its pole, so a point is
 dispersive exactly where its plasma frequency is non-zero.  An object sets
-all four Drude values of the points it covers.  ``mu`` is 1 everywhere.  A
+all four Drude values of the points it covers.  ``sigma`` is the electric
+conductivity in S/m (default 0, 3D schemes, no ``--use-metamaterials`` needed):
+part of the complex permittivity, painted by the rule of ``eps`` (smoothed the
+same way; an object without the key sets 0 where it covers) and not combined
+with ``omega_p`` on one object.  ``mu`` is 1 everywhere.  A
 cylinder's ``center`` holds its two in-plane coordinates, in x, y, z order of
 the two axes other than ``axis``; ``span`` is its extent along ``axis``.
 
@@ -69,12 +73,12 @@ FLAG_IGNORE_SHIFT = 2
 FLAG_SHARP = 32
 
 # the quantities of ``scene_sample``, by the kernel's index: the plasma frequencies (electric, magnetic) and
-# the collision frequencies of the same poles
-QUANTITIES = ("eps", "omega", "omega_m", "gamma", "gamma_m")
+# the collision frequencies of the same poles; "cond" is the conductivity (the key ``sigma``), painted like eps
+QUANTITIES = ("eps", "omega", "omega_m", "gamma", "gamma_m", "cond")
 
 SHAPES = ("box", "sphere", "cylinder", "mesh")
 SMOOTHINGS = ("linear", "none")
-_MEDIUM = {"eps", "omega_p", "gamma", "omega_pm", "gamma_m"}
+_MEDIUM = {"eps", "omega_p", "gamma", "omega_pm", "gamma_m", "sigma"}
 _KEYS = {"box": {"shape", "lo", "hi"} | _MEDIUM,
          "sphere": {"shape", "center", "radius"} | _MEDIUM,
          "cylinder": {"shape", "axis", "center", "radius", "span"} | _MEDIUM,
@@ -122,6 +126,7 @@ class SceneObject:
     gamma: float = 0.0      # electric collision frequency, in units of 2 pi f_source like omega_p
     omega_pm: float = 0.0   # magnetic Drude plasma frequency
     gamma_m: float = 0.0    # magnetic collision frequency
+    sigma: float = 0.0      # electric conductivity, S/m
 
 
 def _number(v, what: str) -> float:
@@ -303,6 +308,12 @@ def parse_object(o, index: int = 0, base_dir: Optional[str] = None) -> SceneObje
         raise ValueError("scene: %sgamma needs omega_p > 0: a damping without a pole" % what)
     if drude["gamma_m"] > 0 and drude["omega_pm"] == 0:
         raise ValueError("scene: %sgamma_m needs omega_pm > 0: a damping without a pole" % what)
+    drude["sigma"] = _number(o.get("sigma", 0.0), what + "sigma")
+    if drude["sigma"] < 0:
+        raise ValueError("scene: %ssigma must not be negative, got %r" % (what, drude["sigma"]))
+    if drude["sigma"] > 0 and omega_p > 0:
+        raise ValueError("scene: %ssigma and omega_p on one object: the pole's cells run the D/B chain, which has "
+                         "no conductive term" % what)
     if shape == "mesh":
         mesh, lo, hi = _mesh(o, what, base_dir)
         return SceneObject("mesh", lo, hi, eps=eps, omega_p=omega_p, mesh=mesh, **drude)
@@ -347,15 +358,54 @@ def parse_objects(objects: Sequence, smoothing: str = "linear",
 
 def check_scheme(objects: Sequence[SceneObject], scheme: str) -> None:
     """What a scheme refuses: every file scene in 1D, a cylinder that does
-    not lie along the inactive axis in 2D, a mesh in 2D."""
+    not lie along the inactive axis in 2D, a mesh in 2D, a conductivity in
+    2D."""
     if scheme == "1d":
         raise ValueError("scene: file scenes need a 2D or 3D scheme")
+    if scheme != "3d":
+        for n, o in enumerate(objects):
+            if o.sigma > 0:
+                raise ValueError("scene: object %d: sigma needs a 3D scheme" % n)
     if scheme in ("tmz", "tez"):
         for n, o in enumerate(objects):
             if o.shape == "cylinder" and o.axis != 2:
                 raise ValueError("scene: object %d: a cylinder of a 2D scheme must lie along z, the inactive axis" % n)
             if o.shape == "mesh":
                 raise ValueError("scene: object %d: a mesh needs a 3D scheme" % n)
+
+
+def lossy_bbox(objects: Sequence[SceneObject]) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
+    """The cell box that holds every lossy object (``sigma > 0``) with the
+    cell of smoothing and of component averaging around it: an upper bound
+    of the lossy box, known before anything is sampled."""
+    lo, hi = [1 << 30] * 3, [-(1 << 30)] * 3
+    for o in objects:
+        if o.sigma <= 0:
+            continue
+        if o.shape in ("box", "mesh"):
+            a, b = list(o.a), list(o.b)
+        else:
+            a, b = [v - o.radius for v in o.a], [v + o.radius for v in o.a]
+            if o.shape == "cylinder":
+                a[o.axis], b[o.axis] = o.a[o.axis], o.b[o.axis]
+        for d in range(3):
+            lo[d] = min(lo[d], int(math.floor(a[d])) - 2)
+            hi[d] = max(hi[d], int(math.ceil(b[d])) + 2)
+    return tuple(lo), tuple(hi)
+
+
+def refuse_lossy_config(cfg, objects: Sequence[SceneObject]) -> Optional[str]:
+    """Why the configuration cannot run with the lossy media (``sigma > 0``)
+    of its scene (None: it can, or there are none)."""
+    if not any(o.sigma > 0 for o in objects):
+        return None
+    if cfg.complex_values:
+        return "scene: sigma with --complex-field-values: the conductive update runs on real fields"
+    if cfg.use_amp_mode:
+        return "scene: sigma with --use-amp-mode: amplitude mode has no conductive update"
+    if cfg.use_hip_graph:
+        return "scene: sigma with --use-hip-graph: the captured steps have no conductive update"
+    return None
 
 
 def parse_scene(doc, base_dir: Optional[str] = None) -> Tuple[Tuple[SceneObject, ...], str]:
@@ -398,11 +448,12 @@ class SceneTable:
     to ``ranges[o, 0] + ranges[o, 1]`` of ``tris`` = (n, 3, 3) fp64 (vertices in
     the order of :class:`Mesh`), ``ranges`` = (objects, 2) int32, zero for every
     other kind.  ``drude`` = (objects, 3) fp64 travels beside the entries: an
-    object's (gamma_e, omega_m, gamma_m) in rad/s, zeros by default.
+    object's (gamma_e, omega_m, gamma_m) in rad/s, zeros by default; so does
+    ``cond`` = (objects,) fp64, an object's conductivity in S/m.
     ``device_tables`` caches the HIP backend's copies, one per device."""
 
     def __init__(self, ents: np.ndarray, tris: Optional[np.ndarray] = None, ranges: Optional[np.ndarray] = None,
-                 drude: Optional[np.ndarray] = None):
+                 drude: Optional[np.ndarray] = None, cond: Optional[np.ndarray] = None):
         if ents.dtype != SCENE_ENT or ents.ndim != 1:
             raise ValueError("SceneTable: a 1D array of SCENE_ENT records")
         if len(ents) > SCENE_MAX_OBJECTS:
@@ -420,6 +471,11 @@ class SceneTable:
             raise ValueError("SceneTable: drude of shape (objects, 3), float64")
         if not np.isfinite(drude).all() or (drude < 0).any():
             raise ValueError("SceneTable: drude values must be finite and not negative")
+        cond = np.zeros((len(ents),), dtype=np.float64) if cond is None else cond
+        err = cond_error(cond, len(ents))
+        if err:
+            raise ValueError("SceneTable: " + err)
+        self.cond = cond
         self.ents = ents
         self.tris = tris
         self.ranges = ranges
@@ -442,6 +498,14 @@ class SceneTable:
         return None
 
 
+def cond_error(cond, nobj: int) -> Optional[str]:
+    """Why ``cond`` is no conductivity table of ``nobj`` objects (None: it is one)."""
+    if (not isinstance(cond, np.ndarray) or cond.dtype != np.float64 or cond.shape != (nobj,)
+            or not np.isfinite(cond).all() or (cond < 0).any()):
+        return "cond of shape (%d,), float64, finite and not negative" % nobj
+    return None
+
+
 def build_table(objects: Sequence[SceneObject], scheme: str = "3d", smoothing: str = "linear",
                 source_frequency: float = 1.0) -> SceneTable:
     objects = parse_objects(list(objects), smoothing)
@@ -449,6 +513,7 @@ def build_table(objects: Sequence[SceneObject], scheme: str = "3d", smoothing: s
     ents = np.zeros(len(objects), dtype=SCENE_ENT)
     ranges = np.zeros((len(objects), 2), dtype=np.int32)
     drude = np.zeros((len(objects), 3), dtype=np.float64)
+    cond = np.array([o.sigma for o in objects], dtype=np.float64).reshape(len(objects))
     tris, first = [], 0
     ignore = 0 if scheme == "3d" else 4  # 2D: objects ignore z
     for n, (e, o) in enumerate(zip(ents, objects)):
@@ -463,14 +528,14 @@ def build_table(objects: Sequence[SceneObject], scheme: str = "3d", smoothing: s
             ranges[n] = (first, len(o.mesh))
             tris.append(o.mesh.tris)
             first += len(o.mesh)
-    return SceneTable(ents, np.concatenate(tris) if tris else None, ranges, drude)
+    return SceneTable(ents, np.concatenate(tris) if tris else None, ranges, drude, cond)
 
 
 def sample_args(quantity: str, points, origin, shape, stride, mod):
     """The arguments of ``scene_sample`` checked and normalised (both
     backends): (quantity index, points, origin, shape, stride, mod)."""
     if quantity not in QUANTITIES:
-        raise ValueError("scene_sample: quantity eps, omega, omega_m, gamma or gamma_m, got %r" % (quantity,))
+        raise ValueError("scene_sample: quantity eps, omega, omega_m, gamma, gamma_m or cond, got %r" % (quantity,))
     pts = [tuple(int(v) for v in p) for p in points]
     if len(pts) not in (1, 2, 4, 8) or any(len(p) != 3 for p in pts):
         raise ValueError("scene_sample: 1, 2, 4 or 8 points of 3 offsets, got %d" % len(pts))

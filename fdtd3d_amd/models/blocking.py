@@ -199,7 +199,8 @@ class BlockedStepping:
         if (self.planes != 1 or cfg.use_amp_mode or self.graph_mode
                 or not self.use_upml_chain or getattr(self, "chain_regions", None) is None or self.use_cpml
                 or getattr(cfg, "dispersion", "drude") != "drude" or self.hooks
-                or getattr(self, "source_list", None) is not None):  # (a source list: the stepped dispersive box)
+                or getattr(self, "source_list", None) is not None  # (a source list: the stepped dispersive box)
+                or getattr(self, "lossy", None) is not None):  # (so does a lossy box)
             return None
         if any("D1" in self.upml[c] for c in self.h_comps) or not any("D1" in self.upml[c] for c in self.e_comps):
             return None
@@ -470,7 +471,8 @@ class BlockedStepping:
         # a source list (layout/source_file.py): the blocked kernels know one hard point only, so such runs
         # keep blocked throughput through a hybrid plan whose stepped windows cover the sources -- with or
         # without absorbing layers
-        sources = getattr(self, "source_list", None) is not None
+        # a lossy box (scene-file key sigma) likewise: the blocked kernels have no factor on the old field
+        sources = getattr(self, "source_list", None) is not None or getattr(self, "lossy", None) is not None
         dg = self._drude_glob
         if dg is not None and not self.fused and self.tb == 1 and dg[0] <= hmax:
             if not (cfg.use_pml or cfg.use_tfsf):
@@ -485,7 +487,7 @@ class BlockedStepping:
                 or not (cfg.use_pml or cfg.use_tfsf or cfg.use_metamaterials or sources) or H > hmax):
             return
         if sources and self.halo is not None:
-            return  # decomposed runs with a source list: the stepped / deep-halo path
+            return  # decomposed runs with a source list or a lossy box: the stepped / deep-halo path
         if self.halo is not None and (cfg.scheme != "3d" or self.domain.buffer_size != H):
             # decomposed: one T-deep exchange per pass feeds both the core and
             # the deep-halo stepped shell, so the ghosts must be exactly T deep
@@ -624,6 +626,10 @@ class BlockedStepping:
         sbox = self.source_list.bbox() if getattr(self, "source_list", None) is not None else None
         if sbox is not None:
             disp.append(sbox)
+        # and the lossy box: the conductive update runs in the stepped windows
+        lbox = self.lossy["gbox"] if getattr(self, "lossy", None) is not None else None
+        if lbox is not None:
+            disp.append(lbox)
         D = None
         for b in disp:
             D = b if D is None else (tuple(min(D[0][d], b[0][d]) for d in range(3)),
@@ -644,7 +650,7 @@ class BlockedStepping:
         if core_cells < 0.25 * size[0] * size[1] * size[2]:
             return None
         # verify: no irregular cell within T + 1 of an output box
-        irregular = [sbox] if sbox is not None else []
+        irregular = [b for b in (sbox, lbox) if b is not None]
         if getattr(self, "chain_regions", None) is not None:
             for kind in ("E", "H"):
                 for r, _ in self.chain_regions[kind]["chain"]:

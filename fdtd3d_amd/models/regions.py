@@ -51,3 +51,30 @@ class RegionLevel:
 
     def cells(self) -> int:
         return sum(box_volume(b) for b in self.boxes)
+
+
+class LossyCoefs:
+    """The (ca, cb) of the conductive E update ``E = ca * E + cb * curl(H)``
+    (``ops.curl_update_lossy``) of every E component, one pair per cell, over
+    one storage box shared by the components: the lossy box, its z range
+    widened to whole groups of four cells so that a 16-byte lane of a field
+    row and the lane of its coefficients are aligned alike
+    (``csrc/lossy_kernels.hip``).  Cells without loss hold ``ca = 1`` and the
+    plain ``cb``; the widened cells are never read for an update."""
+
+    def __init__(self, box: Box, comps, dtype, device):
+        lo, hi = box
+        self.box = ((lo[0], lo[1], lo[2] // 4 * 4), (hi[0], hi[1], -(-hi[2] // 4) * 4))
+        shape = tuple(self.box[1][d] - self.box[0][d] for d in range(3))
+        self.ca = {c: torch.ones(shape, dtype=dtype, device=device) for c in comps}
+        self.cb = {c: torch.zeros(shape, dtype=dtype, device=device) for c in comps}
+
+    def slices(self, box: Box):
+        """The slices of the local ``box`` in the stored arrays."""
+        b = self.box
+        if any(box[0][d] < b[0][d] or box[1][d] > b[1][d] for d in range(3)):
+            raise ValueError("box %s is not inside the lossy storage box %s" % (box, b))
+        return tuple(slice(box[0][d] - b[0][d], box[1][d] - b[0][d]) for d in range(3))
+
+    def cells(self) -> int:
+        return box_volume(self.box)

@@ -43,7 +43,7 @@ from ..layout.yee import (E_COMPONENTS, H_COMPONENTS, MATERIAL_STENCIL, MATERIAL
                           YeeLayout)
 from ..layout.approximation import approximate_material
 from ..ops.coef import Coef
-from .regions import RegionLevel
+from .regions import LossyCoefs, RegionLevel
 from ..parallel.domain import Domain, box_empty, box_intersect, box_subtract
 from ..utils.assertions import FdtdError, fdtd_assert
 from ..utils.constants import ACCURACY, EPS0, MU0, PI, SPEED_OF_LIGHT
@@ -345,11 +345,17 @@ class YeeScheme(BlockedStepping):
         t0 = time.perf_counter()
         dom = self.domain
         shape = dom.shape
+        self.scene = Scene.from_config(cfg, self.source_frequency)
+        if self.scene.kind == "file":
+            # a lossy medium (scene-file key sigma) with an option it cannot run with: before anything is allocated
+            from ..layout.scene_file import refuse_lossy_config
+            why = refuse_lossy_config(cfg, self.scene.objects)
+            if why:
+                raise FdtdError(why)
         self.mem_plan = self.capacity_plan()
         self._check_capacity(self.mem_plan)
         self.F: List[Dict[str, torch.Tensor]] = [{c: self._zeros() for c in self.comps} for _ in range(self.planes)]
 
-        self.scene = Scene.from_config(cfg, self.source_frequency)
         vacuum = self.scene.is_vacuum(cfg.use_metamaterials)
         self.vacuum = vacuum
         sampler = MaterialSampler(self.layout, self.scene, dom.origin, shape, self.device, ops=self.ops)
@@ -392,6 +398,7 @@ class YeeScheme(BlockedStepping):
         if cfg.use_tfsf:
             self._init_tfsf()
         self._init_source()
+        self._init_lossy()
         if cfg.use_amp_mode:
             # one [x][component][y][z] buffer per plane: the maxima of one x
             # plane of all components are contiguous, so the blocked amplitude
@@ -406,13 +413,14 @@ class YeeScheme(BlockedStepping):
         # hard E point source
         self.fused = (cfg.use_fused and hasattr(self.ops, "fused_step") and cfg.scheme == "3d"
                       and not self.use_upml_chain and not self.use_cpml and not cfg.use_tfsf
-                      and not cfg.use_amp_mode and self.source_list is None)
+                      and not cfg.use_amp_mode and self.source_list is None and self.lossy is None)
         # plain 3D runs with TF/SF injection: the fp32 blocked kernel applies
         # the corrections itself (models/tfsf.py TfsfSets), so such serial runs
         # take blocked passes like plain ones (single steps keep the tables)
         self.tfsf_blocked = (cfg.use_tfsf and getattr(self, "tfsf_sets", None) is not None and cfg.use_fused
                              and cfg.scheme == "3d" and not self.use_upml_chain and not self.use_cpml
-                             and not cfg.use_amp_mode and self.halo is None and self.source_list is None)
+                             and not cfg.use_amp_mode and self.halo is None and self.source_list is None
+                             and self.lossy is None)
         if self.fused or self.tfsf_blocked:
             self.F_alt = [{c: self._zeros() for c in self.comps} for _ in range(self.planes)]
         # HIP graph mode (--use-hip-graph): serial HIP runs capture GRAPH_STEPS
@@ -474,7 +482,8 @@ class YeeScheme(BlockedStepping):
         self._drude_plan = self._plan_drude_blk()
         self._init_hybrid()
         if (self.hybrid is None and cfg.scheme == "3d" and self.ops.name == "hip"
-                and getattr(self, "chain_regions", None) is not None and getattr(self, "_chain_prof", None) is not None):
+                and getattr(self, "chain_regions", None) is not None and getattr(self, "_chain_prof", None) is not None
+                and self.lossy is None):  # (a lossy box was checked against the exact slabs: they stay)
             # stepped 3D runs: the z PML slabs' chain boxes widened to whole
             # 128-byte row segments (their 10-cell rows read a third of each
             # line; the widened cells have sigma = 0, where the chain is the
@@ -561,6 +570,15 @@ class YeeScheme(BlockedStepping):
             pml = self.layout.pml_size
             slab = sum(2 * pml[a] * (cells // max(1, n[a])) for a in range(3) if self.layout.active(a))
             plan["cpml_psi"] = 2 * 4 * isz * slab * planes  # ~4 terms per slab cell, two copies
+        if scene.kind == "file" and scene.uniform("cond") != 0.0:
+            # a lossy medium: (ca, cb) per E component over the lossy box, bounded here by the lossy objects'
+            # bounding box (one cell of smoothing and averaging per side)
+            from ..layout.scene_file import lossy_bbox
+            lb = lossy_bbox(scene.objects)
+            vol = 1
+            for a in range(3):
+                vol *= max(0, min(n[a], lb[1][a] - self.domain.origin[a]) - max(0, lb[0][a] - self.domain.origin[a]))
+            plan["lossy_coef"] = 6 * isz * vol
         plan["init_transient"] = 4 * 8 * cells if not scene.is_vacuum(cfg.use_metamaterials) else 0
         if cfg.scene == "file" and plan["init_transient"]:
             # no eps-layout grid: scene_sample writes the averaged fp64 material of a component directly;
@@ -1125,6 +1143,106 @@ class YeeScheme(BlockedStepping):
             ent.rows[kind] = rows[kind]
         self._src_entries = ent
 
+    def _init_lossy(self) -> None:
+        """The lossy box of a file scene with ``sigma`` and its coefficients
+        (``self.lossy``; None without the key: nothing is allocated and no
+        pass changes).  Per E component, eps_r and sigma averaged at it::
+
+            s = sigma dt / (2 eps0 eps_r),  ca = (1 - s) / (1 + s),  cb = dt / (eps0 eps_r dx) / (1 + s)
+
+        evaluated in fp64 (the semi-implicit form: the exponential form's ca
+        underflows in fp32, a pre-scaled plain coefficient has no value at
+        s = 1).  The box is the GLOBAL bounding box of the cells whose averaged
+        sigma is not 0 on any E component -- decomposed ranks agree on it, so
+        a cell takes the same kernel whichever rank holds it -- clipped to
+        each component's update range; its cells without loss hold ca = 1 and
+        the plain cb.  Refused here, since it needs the sampled materials: a
+        box that touches an absorbing layer or a D/B-chain box, or that comes
+        within 2 cells of a TF/SF target cell."""
+        self.lossy = None
+        cfg = self.cfg
+        if self.scene.kind != "file" or self.sampler.uniform("cond") == 0.0:
+            return
+        dom = self.domain
+        dt, dx = self.dt, self.dx
+        alloc = dom.allocated_global()
+        sig = {c: self.sampler.averaged(c, "cond") for c in self.e_comps}
+        big = 1 << 30
+        lo, hi = [big] * 3, [-big] * 3
+        for c in self.e_comps:
+            ub = self.local_box(c, alloc)
+            if box_empty(ub):
+                continue
+            sl = tuple(slice(ub[0][d], ub[1][d]) for d in range(3))
+            nz = torch.nonzero(sig[c][sl] != 0)
+            if nz.shape[0]:
+                for d in range(3):
+                    lo[d] = min(lo[d], int(nz[:, d].min()) + ub[0][d] + dom.origin[d])
+                    hi[d] = max(hi[d], int(nz[:, d].max()) + 1 + ub[0][d] + dom.origin[d])
+        if self.halo is not None:
+            for d in range(3):
+                lo[d] = -int(self.halo.allreduce_max(float(-lo[d])))
+                hi[d] = int(self.halo.allreduce_max(float(hi[d])))
+        if any(hi[d] <= lo[d] for d in range(3)):
+            return  # (every conductive point lies outside the update ranges)
+        G = (tuple(lo), tuple(hi))
+        size = cfg.size
+
+        def grow(b, n):
+            return (tuple(v - n for v in b[0]), tuple(v + n for v in b[1]))
+
+        why = None
+        if cfg.use_pml:
+            for a in range(3):
+                p = self.layout.pml_size[a] if self.layout.active(a) else 0
+                if p > 0 and (G[0][a] <= p or G[1][a] >= size[a] - p):
+                    why = ("scene: the lossy box %s..%s touches the absorbing layer along axis %d (%d cells): a "
+                           "lossy medium must end at least one cell before it" % (G[0], G[1], a, p))
+        regions = getattr(self, "chain_regions", None)
+        if why is None and self.use_upml_chain and regions is None:
+            why = "scene: sigma with the D/B chain on every cell (this UPML configuration): use --pml-type cpml"
+        if why is None and self.use_upml_chain:
+            g1 = grow(G, 1)  # (the chain boxes are global, clipped to this rank)
+            for kind in ("E", "H"):
+                for r, _ in regions[kind]["chain"]:
+                    for c, b in r.items():
+                        if why is None and not box_empty(b) and not box_empty(box_intersect(g1, b)):
+                            gb = b
+                            why = ("scene: the lossy box %s..%s touches a box advanced by the D/B chain (%s %s..%s: "
+                                   "an absorbing slab or a dispersive box)" % (G[0], G[1], c, gb[0], gb[1]))
+        if why is None and cfg.use_tfsf:
+            near = box_intersect(grow(G, 2), alloc)
+            if not box_empty(near) and self._tfsf_targets_in(dom.to_local(near)):
+                why = ("scene: the lossy box %s..%s comes within 2 cells of a TF/SF face: the corrections there "
+                       "take the plain coefficients" % (G[0], G[1]))
+        # decomposed: the chain boxes and TF/SF targets are this rank's, so the ranks vote and refuse together
+        if self.halo is not None and self.halo.allreduce_max(1.0 if why else 0.0) > 0 and why is None:
+            why = "scene: the lossy box %s..%s is refused on another rank" % (G[0], G[1])
+        if why:
+            raise FdtdError(why)
+        store = box_intersect(G, alloc)
+        self.lossy = {"gbox": G, "coefs": None}
+        if box_empty(store):
+            return  # (a decomposed rank the box misses: the same pass structure, nothing to update)
+        coefs = LossyCoefs(dom.to_local(store), self.e_comps, self.dtype, self.device)
+        for c in self.e_comps:
+            lb = self.local_box(c, store)
+            if box_empty(lb):
+                continue
+            sl = tuple(slice(lb[0][d], lb[1][d]) for d in range(3))
+            eps = self.mat[c][sl].to(torch.float64) if self.mat[c] is not None else 1.0
+            sg = sig[c][sl].to(torch.float64)
+            sh = sg * dt / (2 * EPS0 * eps)
+            ca = (1 - sh) / (1 + sh)
+            cb = dt / (EPS0 * eps * dx) / (1 + sh)
+            plain = self.cb[c].materialize(sl)
+            if not isinstance(plain, torch.Tensor):
+                plain = torch.full(sg.shape, float(plain), dtype=self.dtype, device=self.device)
+            cs = coefs.slices(lb)
+            coefs.ca[c][cs] = ca.to(self.dtype)
+            coefs.cb[c][cs] = torch.where(sg == 0, plain.to(self.dtype), cb.to(self.dtype))
+        self.lossy["coefs"] = coefs
+
     def _inject_sources(self, kind: str, t: int) -> None:
         """The source list's entries of ``kind`` after that half step's
         update: one backend op (HIP: one launch), the signals' values at ``tau
@@ -1177,10 +1295,22 @@ class YeeScheme(BlockedStepping):
             # hybrid shell of a decomposed run: clip to this sub-step's deep-halo window
             dw = self._window(kind)
             windows = [b for b in (box_intersect(w, dw) for w in windows) if not box_empty(b)]
+        lossy = []
+        if kind == "E" and getattr(self, "lossy", None) is not None:
+            # a lossy medium: the plain windows lose the lossy box, which runs the conductive update once per
+            # window part (the pieces run the kernels they run today, beside it on the shell streams)
+            G = self.lossy["gbox"]
+            cut = [b for w in windows for b in box_subtract(w, G) if not box_empty(b)]
+            if self.lossy["coefs"] is not None:
+                lossy = [b for b in (box_intersect(w, G) for w in windows) if not box_empty(b)]
+            n_before = len(windows)
+            windows = cut
+        else:
+            n_before = len(windows)
         use_tfsf = self.cfg.use_tfsf
         tfsf_here = use_tfsf and not tfsf_once
         chain = self.use_upml_chain and getattr(self, "chain_regions", None) is not None
-        if chain and self.hybrid is not None and len(windows) > 1:
+        if chain and self.hybrid is not None and n_before > 1:
             # hybrid shell: the chain boxes lie inside the shell, so each runs
             # once, whole; only the plain slabs are cut to the shell windows
             # (decomposed: clipped to this sub-step's deep-halo window)
@@ -1191,7 +1321,7 @@ class YeeScheme(BlockedStepping):
         # hybrid shell without the folded CPML kernels: the psi slabs lie inside
         # the shell, so their corrections run once per slab after all windows
         # (one launch per slab instead of one per slab and window)
-        cpml_once = (self.use_cpml and not fused_cpml and self.hybrid is not None and len(windows) > 1
+        cpml_once = (self.use_cpml and not fused_cpml and self.hybrid is not None and n_before > 1
                      and self.halo is None)
 
         # built (first call: device tensors) on the current stream BEFORE the
@@ -1220,10 +1350,14 @@ class YeeScheme(BlockedStepping):
                     for tab in self.tfsf[c]:
                         self.ops.tfsf_apply(F[c], tab, inc, boxes[c])
 
+        def one_lossy(w):
+            boxes = {c: self.local_box(c, w) for c in comps}
+            self.ops.curl_update_lossy(boxes, F, F, self.lossy["coefs"])
+
         multi = (len(windows) > 1 and not tfsf_here and self.hybrid is not None and not chain
                  and not self.use_upml_chain and not fused_cpml and (not self.use_cpml or cpml_once)
                  and self.cfg.scheme in ("tmz", "tez") and getattr(self.ops, "multi2d", False))
-        multi_cpml = (len(windows) > 1 and not tfsf_here and self.hybrid is not None and not chain and fused_cpml
+        multi_cpml = (n_before > 1 and not tfsf_here and self.hybrid is not None and not chain and fused_cpml
                       and self.cfg.scheme == "3d" and self.multi_cpml and self.halo is not None
                       and hasattr(self.ops, "curl_update_cpml_multi"))
         if multi:
@@ -1236,13 +1370,15 @@ class YeeScheme(BlockedStepping):
             # per row layout (a rank's small windows were launch-bound, profiles/decomp_r6.md)
             self.ops.curl_update_cpml_multi(kind, [{c: self.local_box(c, w) for c in comps} for w in windows], F, F,
                                             self.cb, ktab)
-        elif len(windows) > 1 and not tfsf_here and self.hybrid is not None:
+        elif n_before > 1 and not tfsf_here and self.hybrid is not None:
             # the hybrid shell's windows are disjoint: their launches of a half
             # step are independent and run side by side on several streams
-            self._par_launches([(lambda w=w: one(w)) for w in windows])
+            self._par_launches([(lambda w=w: one(w)) for w in windows] + [(lambda w=w: one_lossy(w)) for w in lossy])
         else:
             for w in windows:
                 one(w)
+            for w in lossy:
+                one_lossy(w)
         if cpml_once:
             alloc = self.domain.allocated_global()
             self.cpml.apply(kind, p, {c: self.local_box(c, alloc) for c in comps})

@@ -208,6 +208,47 @@ class HipOps(HipMonitorOps, HipSceneOps):
             if kind == "H" and box[1][axis] > shape[axis] - 1:
                 raise HipError("H box %s of %s would read past the array along axis %d" % (box, comp, axis))
 
+    def curl_update_lossy(self, boxes: Dict[str, Box], dst: Dict[str, torch.Tensor],
+                          src: Dict[str, torch.Tensor], coefs) -> None:
+        """The contract of ``TorchOps.curl_update_lossy`` in ONE launch of
+        k_lossy_e (csrc/lossy_kernels.hip): Ex, Ey and Ez of a 3D scheme.
+        Checked here, before the launch: every box inside the arrays and the
+        coefficients' storage box, and no curl read outside the arrays.  The
+        kernel takes 16-byte z lanes when the rows of the fields and of the
+        storage box are whole lanes, one cell a lane otherwise
+        (``self.lossy_lanes`` afterwards: 4 / 2 or 1)."""
+        names, other = ("Ex", "Ey", "Ez"), ("Hx", "Hy", "Hz")
+        if self.layout.scheme != "3d" or set(boxes) - set(names):
+            raise HipError("curl_update_lossy: the E components of a 3D scheme")
+        shape = tuple(dst[names[0]].shape)
+        empty = ((0, 0, 0), (0, 0, 0))
+        bs = [boxes.get(c, empty) for c in names]
+        rb = coefs.box
+        rshape = tuple(rb[1][d] - rb[0][d] for d in range(3))
+        for c, b in zip(names, bs):
+            self._check_tensor(dst[c], shape)
+            self._check_tensor(coefs.ca[c], rshape)
+            self._check_tensor(coefs.cb[c], rshape)
+            if not _empty(b):
+                self._check_stencil_box("E", c, b, shape)
+                if any(b[0][d] < rb[0][d] or b[1][d] > rb[1][d] for d in range(3)):
+                    raise HipError("box %s of %s outside the coefficients' storage box %s" % (b, c, rb))
+        for c in other:
+            self._check_tensor(src[c], shape)
+        if all(_empty(b) for b in bs):
+            return
+        vp3 = c_vp * 3
+        lanes = c_int(0)
+        rc = self.fn("lossy_e")(vp3(*[dst[c].data_ptr() for c in names]), vp3(*[src[c].data_ptr() for c in other]),
+                                vp3(*[coefs.ca[c].data_ptr() for c in names]),
+                                vp3(*[coefs.cb[c].data_ptr() for c in names]),
+                                c_int(shape[0]), c_int(shape[1]), c_int(shape[2]),
+                                _box_arr([b if not _empty(b) else empty for b in bs]), _box_arr([rb]), _stream(),
+                                ctypes.byref(lanes))
+        _check(rc, "curl_update_lossy")
+        self.lossy_lanes = int(lanes.value)  # cells per lane of the instance that ran (4 / 2: 16 bytes; 1)
+        self.launches += 1
+
     def _coef_args(self, c: Coef):
         ps = (c_vp * 4)(*[None if t is None else t.data_ptr() for t in (c.px, c.py, c.pz, c.cell)])
         for t in (c.px, c.py, c.pz, c.cell):

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 import torch
 
-from ..layout.scene_file import (SCENE_ENT_SIZE, SCENE_MAX_OBJECTS, SCENE_MAX_TRIANGLES, SceneTable,
+from ..layout.scene_file import (cond_error, SCENE_ENT_SIZE, SCENE_MAX_OBJECTS, SCENE_MAX_TRIANGLES, SceneTable,
                                  sample_args)
 from .hip_lib import HipError, _check, _ptr, _stream, c_double, c_int
 
@@ -66,12 +66,24 @@ class HipSceneOps:
             dev = table.device_tables[key] = host.to(self.device)
         return dev
 
+    def _scene_cond(self, table: SceneTable) -> torch.Tensor:
+        """``table.cond`` on the device: a double an object (at least one, so
+        never a null pointer); cached on ``table`` per device."""
+        key = str(torch.device(self.device)) + " cond"
+        dev = table.device_tables.get(key)
+        if dev is None:
+            host = torch.zeros((max(1, len(table)),), dtype=torch.float64)
+            host[:len(table)] = torch.from_numpy(table.cond.copy())
+            dev = table.device_tables[key] = host.to(self.device)
+        return dev
+
     def scene_sample(self, table, quantity: str, points, origin, shape, stride, mod, out=None,
                      cull: bool = True) -> torch.Tensor:
         """The contract of ``TorchOps.scene_sample`` in ONE launch of
         k_scene_sample (k_scene_sample_mesh when the table holds a mesh;
         k_scene_sample_drude and its mesh twin for omega_m, gamma and gamma_m,
-        which read ``table.drude`` too).  ``out``: a contiguous fp64 device
+        which read ``table.drude`` too; k_scene_sample_cond and its mesh twin
+        for cond, which read ``table.cond``).  ``out``: a contiguous fp64 device
         tensor of ``shape`` to fill (allocated otherwise); ``cull`` = False
         evaluates every object at every cell (measurements)."""
         if not isinstance(table, SceneTable):
@@ -87,6 +99,9 @@ class HipSceneOps:
         if (not isinstance(drude, np.ndarray) or drude.dtype != np.float64 or drude.shape != (len(table), 3)
                 or not np.isfinite(drude).all() or (drude < 0).any()):
             raise HipError("scene_sample: drude of shape (%d, 3), float64, finite and not negative" % len(table))
+        err = cond_error(getattr(table, "cond", None), len(table))
+        if err:
+            raise HipError("scene_sample: " + err)
         try:
             q, pts, origin, shape, stride, mod = sample_args(quantity, points, origin, shape, stride, mod)
         except ValueError as e:
@@ -106,14 +121,17 @@ class HipSceneOps:
         args = (_ptr(tab), c_int(len(table)), c_int(q), (ctypes.c_int * len(flat))(*flat), c_int(len(pts)),
                 i3(*origin), i3(*shape), i3(*stride), c_double(mod), c_int(1 if cull else 0), _ptr(out), _stream())
         raw = self.lib.raw
-        if q >= 2:   # omega_m, gamma, gamma_m: the second table
+        if q == 5:   # cond: the conductivities
+            args += (_ptr(self._scene_cond(table)), c_int(len(table.cond)))
+        elif q >= 2:   # omega_m, gamma, gamma_m: the second table
             args += (_ptr(self._scene_drude(table)), c_int(len(drude)))
+        name = "fdtd_scene_sample" + ("_cond" if q == 5 else "_drude" if q >= 2 else "")
         if meshes:
             tris, ranges = self._scene_triangles(table)
-            f = raw.fdtd_scene_sample_drude_mesh if q >= 2 else raw.fdtd_scene_sample_mesh
+            f = getattr(raw, name + "_mesh")
             args += (_ptr(tris), c_int(len(table.tris)), _ptr(ranges))
         else:
-            f = raw.fdtd_scene_sample_drude if q >= 2 else raw.fdtd_scene_sample
+            f = getattr(raw, name)
         f.restype = c_int
         rc = f(*args)
         _check(rc, "scene_sample")

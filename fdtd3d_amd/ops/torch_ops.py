@@ -10,6 +10,9 @@ Operation semantics (shared by both backends):
 * ``curl_update(kind, boxes, dst, src, cb)`` -- fast path
   ``dst[c] += cb[c] * curl(src)[c]`` on each component's local box.  ``curl``
   follows :data:`fdtd3d_amd.layout.yee.CURL_TERMS` (reference ``Kernels.h``).
+* ``curl_update_lossy(boxes, dst, src, coefs)`` -- the E update of a lossy box,
+  ``dst[c] = ca[c] * dst[c] + cb[c] * curl(src)[c]`` with box-local per-cell
+  coefficients.
 * ``curl_general(kind, comp, box, out, inp, src, ca, cb)`` --
   ``out = ca*inp + cb*curl(src)`` (UPML D/B update, ``Scheme3D.cpp:266-324``).
 * ``lincomb(out, box, terms)`` -- ``out = sum coef_i * x_i`` (Drude ADE and
@@ -92,6 +95,23 @@ class TorchOps:
             if c is None:
                 continue
             dst[comp][sl] += cb[comp].materialize(sl) * c
+
+    def curl_update_lossy(self, boxes: Dict[str, Box], dst: Dict[str, torch.Tensor],
+                          src: Dict[str, torch.Tensor], coefs) -> None:
+        """The conductive E update of a lossy medium, ``dst[c] = ca[c] * dst[c]
+        + cb[c] * curl(src)[c]`` on each E component's local box: ``coefs``
+        (models/regions.py ``LossyCoefs``) holds one (ca, cb) pair per cell
+        over its storage box, which contains every box.  The same ``curl`` as
+        :meth:`curl_update`."""
+        for comp, box in boxes.items():
+            if _empty(box):
+                continue
+            sl = box_slices(box)
+            c = self.curl("E", comp, sl, src)
+            if c is None:
+                continue
+            cs = coefs.slices(box)
+            dst[comp][sl] = coefs.ca[comp][cs] * dst[comp][sl] + coefs.cb[comp][cs] * c
 
     def fused_step(self, fin: Dict[str, torch.Tensor], fout: Dict[str, torch.Tensor], boxes: Dict[str, Box],
                    cb: Dict[str, Coef], source=None) -> None:
@@ -756,6 +776,8 @@ class TorchOps:
         frequency (omega, omega_m) as sqrt(sum(w * w) / n), a collision
         frequency (gamma, gamma_m) as sum(g) / count over the points whose
         plasma frequency of the same kind is not zero, 0 where there is none.
+        The conductivity (cond, ``table.cond``) is painted and reduced exactly
+        as eps is, over 0 instead of 1.
         Every operation is rounded on its own, in the order the kernel of
         csrc/scene_kernels.hip keeps, the square roots correctly (``_sqrt_rn``):
         this is its oracle."""
@@ -780,7 +802,7 @@ class TorchOps:
             for n, e in enumerate(table.ents):
                 # what the object paints: its pole (or eps) and, for a gamma quantity, the pole's damping
                 g_e, w_m, g_m = (float(v) for v in table.drude[n])
-                obj = (float(e["eps"]), float(e["omega"]), w_m, float(e["omega"]), w_m)[q]
+                obj = (float(e["eps"]), float(e["omega"]), w_m, float(e["omega"]), w_m, float(table.cond[n]))[q]
                 obj_damp = g_e if q == 3 else g_m
                 flags = int(e["flags"])
                 skip = [bool((flags >> (FLAG_IGNORE_SHIFT + a)) & 1) for a in range(3)]
@@ -796,7 +818,7 @@ class TorchOps:
                 elif e["kind"] == KIND_MESH:
                     t0, tn = (int(v) for v in table.ranges[n])
                     d = _mesh_distance(table.tris[t0:t0 + tn] * mod, ax, shape,
-                                       q == 0 and not flags & FLAG_SHARP)
+                                       q in (0, 5) and not flags & FLAG_SHARP)
                 elif e["kind"] == KIND_SPHERE:
                     sq = [torch.zeros_like(P[a]) if skip[a] else (P[a] - a0[a]) * (P[a] - a0[a]) for a in range(3)]
                     d = _sqrt_rn((sq[0] + sq[1]) + sq[2]) - b0[0]
@@ -807,21 +829,21 @@ class TorchOps:
                     d = _sqrt_rn(db * db + dc * dc) - b0[0]
                     if not skip[ax_c]:
                         d = torch.maximum(d, torch.maximum(a0[ax_c] - P[ax_c], P[ax_c] - b0[1]))
-                if q >= 1:
+                if 1 <= q <= 4:
                     val = torch.where(d < 0, torch.full_like(val, obj), val)
                     if q >= 3:
                         damp = torch.where(d < 0, torch.full_like(damp, obj_damp), damp)
                 elif flags & FLAG_SHARP:
-                    val = torch.where(d < 0, torch.full_like(val, float(e["eps"])), val)
+                    val = torch.where(d < 0, torch.full_like(val, obj), val)
                 else:
-                    eps_in = float(e["eps"])
+                    eps_in = obj
                     prop = 0.5 - d
                     mid = prop * eps_in + (1 - prop) * val
                     o = torch.where(d < -0.5, torch.full_like(val, eps_in), mid)
                     val = torch.where(d > 0.5, val, o)
             vals.append(val)
             damps.append(damp)
-        if q == 0:
+        if q in (0, 5):
             res = approximate_material(vals)
         elif q <= 2:
             res = _sqrt_rn(sum(w * w for w in vals) / float(len(vals)))

@@ -184,6 +184,13 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
         except ValueError as e:
             out.write("ERROR: %s\n" % e)
             return EXIT_ERROR
+    if cfg0.scene == "file" and cfg0.scene_objects:
+        # a lossy medium (sigma) with an option it cannot run with
+        from .layout.scene_file import refuse_lossy_config
+        why = refuse_lossy_config(cfg0, cfg0.scene_objects)
+        if why:
+            out.write("ERROR: %s\n" % why)
+            return EXIT_ERROR
     if (settings.doUseDft or settings.doUseNtffDft or settings.doUseFlux or settings.doUseFarfield
             or settings.doUseEnergy or settings.stopDecayBy != 0 or settings.doUseProbes):
         # refused before anything is set up, never a silent fallback (models/dft.py, models/energy.py,
@@ -422,7 +429,8 @@ def run(argv: Optional[List[str]] = None, out=sys.stdout) -> int:
                 if triangles:   # (a scene with meshes: their triangles)
                     rec["scene"]["triangles"] = triangles
                 # (Drude media beyond a lossless electric pole: the objects with damping / a magnetic pole)
-                for key, field in (("damped", "gamma"), ("magnetic", "omega_pm")):
+                # and the lossy ones (sigma)
+                for key, field in (("damped", "gamma"), ("magnetic", "omega_pm"), ("lossy", "sigma")):
                     count = sum(getattr(o, field) > 0 for o in scheme.scene.objects)
                     if count:
                         rec["scene"][key] = count
