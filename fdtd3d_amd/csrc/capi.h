@@ -2,6 +2,7 @@
 // The Python side binds the same symbols through ctypes (ops/hip_ops.py).
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 extern "C" {
@@ -271,32 +272,16 @@ int fdtd_source_inject_f64(const void* tab, int n, const double* values, int nva
 int fdtd_source_ent_size();
 int fdtd_source_max_signals();
 
-// file scenes (scene_kernels.hip): the magnetic Drude plasma frequency and the
-// collision frequencies of a component.  tab, points, origin, shape, stride,
-// mod, cull, out as fdtd_scene_sample; quantity 2 = omega_m, 3 = gamma, 4 =
-// gamma_m; drude = ndrude (== nobj) device triples (gamma_e, omega_m, gamma_m)
-// of fdtd_scene_drude_size() bytes, rad/s.  The mesh form adds the triangle
-// tables of fdtd_scene_sample_mesh.  hipErrorInvalidValue, with nothing
-// launched, for a null pointer, another quantity or ndrude != nobj
-int fdtd_scene_sample_drude(const void* tab, int nobj, int quantity, const int* points, int npts, const int* origin,
-                            const int* shape, const int* stride, double mod, int cull, void* out, void* s,
-                            const void* drude, int ndrude);
-int fdtd_scene_sample_drude_mesh(const void* tab, int nobj, int quantity, const int* points, int npts,
-                                 const int* origin, const int* shape, const int* stride, double mod, int cull,
-                                 void* out, void* s, const void* drude, int ndrude, const void* tris, int ntris,
-                                 const void* ranges);
+// file scenes (scene_kernels.hip): one component's averaged material, quantity 0 = eps, 1 = omega, 2 =
+// omega_m, 3 = gamma, 4 = gamma_m, 5 = cond.  side = the quantity's device side table of side_bytes bytes, a
+// row per object: none (null, 0) for 0 and 1, triples (gamma_e, omega_m, gamma_m) of fdtd_scene_drude_size()
+// bytes, rad/s, for 2 to 4, doubles (S/m) for 5.  ranges (non-null) selects the mesh form and brings tris /
+// ntris; without it tris is null and ntris 0.  hipErrorInvalidValue, with nothing launched, for a null
+// pointer, another quantity, a side table that is not the quantity's or whose size is not nobj rows
+int fdtd_scene_sample(const void* tab, int nobj, int quantity, const int* points, int npts, const int* origin,
+                      const int* shape, const int* stride, double mod, int cull, void* out, void* s, const void* side,
+                      size_t side_bytes, const void* tris, int ntris, const void* ranges);
 int fdtd_scene_drude_size();
-
-// file scenes (scene_kernels.hip): the conductivity of a component (the scene-file key sigma), painted by
-// the rule of eps over 0.  Arguments as fdtd_scene_sample; quantity 5; cond = ncond (== nobj) device doubles,
-// S/m.  hipErrorInvalidValue, with nothing launched, for a null pointer, another quantity or ncond != nobj
-int fdtd_scene_sample_cond(const void* tab, int nobj, int quantity, const int* points, int npts, const int* origin,
-                           const int* shape, const int* stride, double mod, int cull, void* out, void* s,
-                           const void* cond, int ncond);
-int fdtd_scene_sample_cond_mesh(const void* tab, int nobj, int quantity, const int* points, int npts,
-                                const int* origin, const int* shape, const int* stride, double mod, int cull,
-                                void* out, void* s, const void* cond, int ncond, const void* tris, int ntris,
-                                const void* ranges);
 
 // the conductive E update of a lossy box (lossy_kernels.hip): E = ca * E + cb * curl(H) on the three boxes
 // (boxes = Ex, Ey, Ez as 6 ints each, local indices) in one launch.  e / h = the three field arrays of

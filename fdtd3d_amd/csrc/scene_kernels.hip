@@ -16,8 +16,14 @@
 // which leaves the value below untouched bit for bit; the test is on
 // wave-uniform values and broadcast, so the branch is a scalar one.
 //
-// A mesh (k_scene_sample_mesh, the same body with the fourth kind compiled in)
-// is one more object of the painter's loop: its entry holds its bounding box,
+// All of it is ONE kernel, k_scene_sample<Q, MESH>: Q the quantity, MESH
+// whether the fourth kind is compiled in.  What Q decides is named once, in the
+// traits q_averaged, q_damped, q_reads_drude and q_reads_cond, and applied with
+// `if constexpr`; a variant that reads no side table, or no mesh tables, gets
+// an empty argument in their place and loads none.  The twelve instantiations
+// are launched from one table (SCENE_LAUNCH) by the one entry point.
+//
+// A mesh (MESH) is one more object of the painter's loop: its entry holds its bounding box,
 // a second table its range of the triangle buffer, which is read like the
 // object table, one triangle per trip of every wave.  Sign: the parity of the
 // triangles a ray along +z crosses (mesh_crossed); magnitude: the distance to
@@ -29,12 +35,13 @@
 // tile: the others lie farther than a cell from every point, which can move a
 // distance only where it stays beyond 0.5 and the painting rule does not read it.
 //
-// The magnetic pole and the collision frequencies (k_scene_sample_drude and its
-// mesh twin, the same body once more) read a second table, an object's
-// (gamma_e, omega_m, gamma_m), the same way.  All are sharp.  A collision
-// frequency paints two values per point, the pole and its damping, and reduces
-// to the mean damping of the points whose pole is not zero (approximate_drude);
-// an object culled for a wave paints neither.
+// The magnetic pole and the collision frequencies (q_reads_drude) read a side
+// table, an object's (gamma_e, omega_m, gamma_m), the same way.  All are sharp.
+// A collision frequency (q_damped) paints two values per point, the pole and
+// its damping, and reduces to the mean damping of the points whose pole is not
+// zero (approximate_drude); an object culled for a wave paints neither.  The
+// conductivity (q_reads_cond: a double per object) is painted and averaged by
+// the rule of eps (q_averaged), over 0.
 #include "common.h"
 #include "monitor_dev.h"
 
@@ -196,89 +203,259 @@ __device__ __forceinline__ double mesh_signed(unsigned parity, bool magnitude, d
   return (parity & 1u) ? -far : far;
 }
 
-template <int Q>  // 0: eps, 1: omega
-__global__ __launch_bounds__(256) void k_scene_sample(const SceneEnt* __restrict__ tab, double* __restrict__ out,
-                                                      SceneArgs A) {
-#define SCENE_WITH_MESH 0
-#define SCENE_WITH_DRUDE 0
-#define SCENE_WITH_COND 0
-#include "scene_body.inc"
-#undef SCENE_WITH_COND
-#undef SCENE_WITH_DRUDE
-#undef SCENE_WITH_MESH
-}
+// What a quantity Q is (layout/scene_file.py sample_args: 0 eps, 1 omega, 2 omega_m, 3 gamma, 4 gamma_m,
+// 5 cond), decided here and nowhere else.
+constexpr bool q_averaged(int Q) { return Q == 0 || Q == 5; }      // painted and averaged like eps
+constexpr bool q_damped(int Q) { return Q == 3 || Q == 4; }        // paints a damping beside the pole
+constexpr bool q_reads_drude(int Q) { return 2 <= Q && Q <= 4; }   // reads the SceneDrude side table
+constexpr bool q_reads_cond(int Q) { return Q == 5; }              // reads the conductivity side table
+enum { SCENE_QUANTITIES = 6 };
 
+// The kernel's side table and mesh tables as typed arguments; a variant that reads none gets SceneNone
+// in their place, which nothing loads.
+struct SceneNone {};
 template <int Q>
-__global__ __launch_bounds__(256) void k_scene_sample_mesh(const SceneEnt* __restrict__ tab,
-                                                           double* __restrict__ out, SceneArgs A, SceneMesh M) {
-#define SCENE_WITH_MESH 1
-#define SCENE_WITH_DRUDE 0
-#define SCENE_WITH_COND 0
-#include "scene_body.inc"
-#undef SCENE_WITH_COND
-#undef SCENE_WITH_DRUDE
-#undef SCENE_WITH_MESH
-}
+using SceneSide = std::conditional_t<q_reads_drude(Q), const SceneDrude* __restrict__,
+                                     std::conditional_t<q_reads_cond(Q), const double* __restrict__, SceneNone>>;
+template <bool MESH>
+using SceneMeshArg = std::conditional_t<MESH, SceneMesh, SceneNone>;
 
-template <int Q>  // 2: omega_m, 3: gamma, 4: gamma_m
-__global__ __launch_bounds__(256) void k_scene_sample_drude(const SceneEnt* __restrict__ tab,
-                                                            const SceneDrude* __restrict__ drude,
-                                                            double* __restrict__ out, SceneArgs A) {
-#define SCENE_WITH_MESH 0
-#define SCENE_WITH_DRUDE 1
-#define SCENE_WITH_COND 0
-#include "scene_body.inc"
-#undef SCENE_WITH_COND
-#undef SCENE_WITH_DRUDE
-#undef SCENE_WITH_MESH
-}
-
+// one point painted with an object at signed distance d: v the value, g the damping beside it
 template <int Q>
-__global__ __launch_bounds__(256) void k_scene_sample_drude_mesh(const SceneEnt* __restrict__ tab,
-                                                                 const SceneDrude* __restrict__ drude,
-                                                                 double* __restrict__ out, SceneArgs A, SceneMesh M) {
-#define SCENE_WITH_MESH 1
-#define SCENE_WITH_DRUDE 1
-#define SCENE_WITH_COND 0
-#include "scene_body.inc"
-#undef SCENE_WITH_COND
-#undef SCENE_WITH_DRUDE
-#undef SCENE_WITH_MESH
+__device__ __forceinline__ void scene_paint(double d, int flags, double obj, double damp, double& v, double& g) {
+#pragma clang fp contract(off)
+  const double below = v;
+  if (!q_averaged(Q) || (flags & SCENE_SHARP)) {
+    v = d < 0.0 ? obj : below;
+    if constexpr (q_damped(Q)) g = d < 0.0 ? damp : g;
+  } else {
+    const double prop = 0.5 - d;
+    const double mid = prop * obj + (1.0 - prop) * below;
+    const double r = d < -0.5 ? obj : mid;
+    v = d > 0.5 ? below : r;
+  }
 }
 
-template <int Q>  // 5: cond
-__global__ __launch_bounds__(256) void k_scene_sample_cond(const SceneEnt* __restrict__ tab,
-                                                           const double* __restrict__ cond,
-                                                           double* __restrict__ out, SceneArgs A) {
-#define SCENE_WITH_MESH 0
-#define SCENE_WITH_DRUDE 0
-#define SCENE_WITH_COND 1
-#include "scene_body.inc"
-#undef SCENE_WITH_COND
-#undef SCENE_WITH_DRUDE
-#undef SCENE_WITH_MESH
+template <int Q, bool MESH>
+__global__ __launch_bounds__(256) void k_scene_sample(const SceneEnt* __restrict__ tab, SceneSide<Q> side,
+                                                      double* __restrict__ out, SceneArgs A, SceneMeshArg<MESH> M) {
+#pragma clang fp contract(off)
+  const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (w >= A.waves) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const unsigned tz = w % A.tz_tiles, t = w / A.tz_tiles;
+  const unsigned ty = t % A.ty_tiles;
+  const int x = (int)(t / A.ty_tiles);
+  const int zlanes = 1 << A.zl, ylanes = 64 >> A.zl;
+  const int y0 = (int)ty * ylanes, z0 = (int)tz * 2 * zlanes;
+  const int y = y0 + (lane >> A.zl), z = z0 + 2 * (lane & (zlanes - 1));
+
+  // the eps-grid points of the wave's tile, per axis (wave-uniform)
+  const int y1 = min(y0 + ylanes, A.n[1]) - 1, z1 = min(z0 + 2 * zlanes, A.n[2]) - 1;
+  const int ilo[3] = {x, y0, z0}, ihi[3] = {x, y1, z1};
+  double wlo[3], whi[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    wlo[c] = (double)(A.base[c] + A.stride[c] * ilo[c] + A.omin[c]) + 0.5;
+    whi[c] = (double)(A.base[c] + A.stride[c] * ihi[c] + A.omax[c]) + 0.5;
+  }
+
+  // the thread's points: cell j (z + j) x point k
+  const int cell[3] = {x, y, z};
+  double px[SCENE_MAX_POINTS], py[SCENE_MAX_POINTS], pz[2][SCENE_MAX_POINTS];
+#pragma unroll
+  for (int k = 0; k < SCENE_MAX_POINTS; ++k) {
+    px[k] = (double)(A.base[0] + A.stride[0] * cell[0] + A.off[k][0]) + 0.5;
+    py[k] = (double)(A.base[1] + A.stride[1] * cell[1] + A.off[k][1]) + 0.5;
+    pz[0][k] = (double)(A.base[2] + A.stride[2] * cell[2] + A.off[k][2]) + 0.5;
+    pz[1][k] = (double)(A.base[2] + A.stride[2] * (cell[2] + 1) + A.off[k][2]) + 0.5;
+  }
+  double v[2][SCENE_MAX_POINTS];
+#pragma unroll
+  for (int k = 0; k < SCENE_MAX_POINTS; ++k) v[0][k] = v[1][k] = Q == 0 ? 1.0 : 0.0;
+  double g[2][SCENE_MAX_POINTS];  // the dampings (read only where q_damped)
+#pragma unroll
+  for (int k = 0; k < SCENE_MAX_POINTS; ++k) g[0][k] = g[1][k] = 0.0;
+
+  const mon::ConstTab<SceneEnt> E = (mon::ConstTab<SceneEnt>)tab;
+  for (int o = 0; o < A.nobj; ++o) {
+    const int kind = E[o].kind, flags = E[o].flags;
+    const double a[3] = {E[o].p[0] * A.mod, E[o].p[1] * A.mod, E[o].p[2] * A.mod};
+    const double b[3] = {E[o].q[0] * A.mod, E[o].q[1] * A.mod, E[o].q[2] * A.mod};
+    if (A.flags & SCENE_CULL) {
+      // the object's bounding box per axis; an ignored axis never culls
+      const int ign = flags >> SCENE_IGNORE_SHIFT, ax = flags & 3;
+      bool miss = false;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        double lo, hi;
+        if (kind == SCENE_BOX || (MESH && kind == SCENE_MESH)) {
+          lo = a[c], hi = b[c];
+        } else if (kind == SCENE_CYLINDER && c == ax) {
+          lo = a[c], hi = b[1];
+        } else {
+          lo = a[c] - b[0], hi = a[c] + b[0];
+        }
+        if (!((ign >> c) & 1)) miss = miss || lo - whi[c] > 1.0 || wlo[c] - hi > 1.0;
+      }
+      if (__builtin_amdgcn_readfirstlane((int)miss)) continue;
+    }
+    // the value a point is painted with (gamma: the electric pole, which decides whether the point is
+    // dispersive) and the damping that goes with it
+    double obj, damp = 0.0;
+    if constexpr (q_reads_drude(Q)) {
+      const mon::ConstTab<SceneDrude> D = (mon::ConstTab<SceneDrude>)side;
+      obj = Q == 3 ? E[o].omega : D[o].omega_m;
+      damp = Q == 3 ? D[o].gamma_e : D[o].gamma_m;
+    } else if constexpr (q_reads_cond(Q)) {
+      obj = ((mon::ConstTab<double>)side)[o];
+    } else {
+      obj = Q == 0 ? E[o].eps : E[o].omega;
+    }
+    if constexpr (MESH) {
+      // a mesh: bit 8 j + k of par = the parity of the triangles crossed above point (j, k), dm = the
+      // squared distance of the closest one (under linear smoothing)
+      const bool is_mesh = kind == SCENE_MESH;
+      const bool magnitude = q_averaged(Q) && !(flags & SCENE_SHARP);
+      unsigned par = 0u;
+      double dm[2][SCENE_MAX_POINTS];
+      if (is_mesh) {
+#pragma unroll
+        for (int k = 0; k < SCENE_MAX_POINTS; ++k) dm[0][k] = dm[1][k] = __builtin_inf();
+        const mon::ConstTab<SceneRange> R = (mon::ConstTab<SceneRange>)M.ranges;
+        const mon::ConstTab<SceneTri> G = (mon::ConstTab<SceneTri>)M.tris;
+        // (the range clamped to the buffer: nothing outside it is ever read)
+        const int t0 = min(max(R[o].first, 0), M.ntris), t1 = t0 + min(max(R[o].count, 0), M.ntris - t0);
+        for (int t = t0; t < t1; ++t) {
+          TriGeom T;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            T.v0[c] = G[t].v[0][c] * A.mod;
+            T.v1[c] = G[t].v[1][c] * A.mod;
+            T.v2[c] = G[t].v[2][c] * A.mod;
+            T.lo[c] = fmin(T.v0[c], fmin(T.v1[c], T.v2[c]));
+            T.hi[c] = fmax(T.v0[c], fmax(T.v1[c], T.v2[c]));
+          }
+          bool hit = true, near = magnitude;
+          if (A.flags & SCENE_CULL) {
+            hit = T.hi[0] >= wlo[0] && T.lo[0] <= whi[0] && T.hi[1] >= wlo[1] && T.lo[1] <= whi[1] && T.hi[2] >= wlo[2];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) near = near && !(T.lo[c] - whi[c] > 1.0 || wlo[c] - T.hi[c] > 1.0);
+          }
+          hit = __builtin_amdgcn_readfirstlane((int)hit) != 0;
+          near = __builtin_amdgcn_readfirstlane((int)near) != 0;
+          if (!hit && !near) continue;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            T.ab[c] = T.v1[c] - T.v0[c];
+            T.ac[c] = T.v2[c] - T.v0[c];
+            T.bc[c] = T.v2[c] - T.v1[c];
+          }
+          T.n[0] = T.ab[1] * T.ac[2] - T.ab[2] * T.ac[1];
+          T.n[1] = T.ab[2] * T.ac[0] - T.ab[0] * T.ac[2];
+          T.n[2] = T.ab[0] * T.ac[1] - T.ab[1] * T.ac[0];
+          if (hit) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+              for (int k = 0; k < SCENE_MAX_POINTS; ++k) {
+                if (k >= A.npts) continue;
+                const double P[3] = {px[k], py[k], pz[j][k]};
+                par ^= (unsigned)mesh_crossed(T, P) << (8 * j + k);
+              }
+          }
+          if (near) {
+            const double nn = dot3(T.n, T.n);
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+              for (int k = 0; k < SCENE_MAX_POINTS; ++k) {
+                if (k >= A.npts) continue;
+                const double P[3] = {px[k], py[k], pz[j][k]};
+                const double ds = mesh_dist2(T, nn, P);
+                dm[j][k] = ds < dm[j][k] ? ds : dm[j][k];  // (a NaN never lowers it)
+              }
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int k = 0; k < SCENE_MAX_POINTS; ++k) {
+          if (k >= A.npts) continue;
+          const double P[3] = {px[k], py[k], pz[j][k]};
+          scene_paint<Q>(is_mesh ? mesh_signed(par >> (8 * j + k), magnitude, dm[j][k]) : scene_dist(kind, flags, a, b, P), flags, obj, damp, v[j][k], g[j][k]);
+        }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int k = 0; k < SCENE_MAX_POINTS; ++k) {
+          if (k >= A.npts) continue;
+          const double P[3] = {px[k], py[k], pz[j][k]};
+          scene_paint<Q>(scene_dist(kind, flags, a, b, P), flags, obj, damp, v[j][k], g[j][k]);
+        }
+    }
+  }
+
+  double res[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if constexpr (q_averaged(Q)) {
+      // the pairwise-hierarchical mean (layout/approximation.py approximate_material)
+      double m[SCENE_MAX_POINTS];
+#pragma unroll
+      for (int k = 0; k < SCENE_MAX_POINTS; ++k) m[k] = v[j][k];
+#pragma unroll
+      for (int step = 1; step < SCENE_MAX_POINTS; step *= 2)
+        if (step < A.npts) {
+#pragma unroll
+          for (int k = 0; k + step < SCENE_MAX_POINTS; k += 2 * step) m[k] = (m[k] + m[k + step]) / 2.0;
+        }
+      res[j] = m[0];
+    } else if constexpr (!q_damped(Q)) {
+      // sqrt(sum(w * w) / n), the sum left to right from 0 (approximate_drude)
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < SCENE_MAX_POINTS; ++k)
+        if (k < A.npts) s = s + v[j][k] * v[j][k];
+      res[j] = __dsqrt_rn(s / (double)A.npts);
+    } else {
+      // sum(g) / count over the dispersive points (pole != 0), both left to right from 0; 0 without one
+      double s = 0.0, n = 0.0;
+#pragma unroll
+      for (int k = 0; k < SCENE_MAX_POINTS; ++k)
+        if (k < A.npts) {
+          s = s + g[j][k];
+          n = n + (v[j][k] != 0.0 ? 1.0 : 0.0);
+        }
+      const double mean = s / (n > 0.0 ? n : 1.0);
+      res[j] = n > 0.0 ? mean : 0.0;
+    }
+  }
+
+  if (y >= A.n[1] || z >= A.n[2]) return;
+  double* o = out + ((size_t)x * (size_t)A.n[1] + (size_t)y) * (size_t)A.n[2] + (size_t)z;
+  if (z + 1 < A.n[2]) {
+    if (A.flags & SCENE_VEC) {
+      typedef double D2 __attribute__((ext_vector_type(2)));
+      *reinterpret_cast<D2*>(o) = D2{res[0], res[1]};  // even z, even rows, an aligned base: 16 bytes
+    } else {
+      o[0] = res[0];
+      o[1] = res[1];
+    }
+  } else {
+    o[0] = res[0];
+  }
 }
 
-template <int Q>
-__global__ __launch_bounds__(256) void k_scene_sample_cond_mesh(const SceneEnt* __restrict__ tab,
-                                                                const double* __restrict__ cond,
-                                                                double* __restrict__ out, SceneArgs A, SceneMesh M) {
-#define SCENE_WITH_MESH 1
-#define SCENE_WITH_DRUDE 0
-#define SCENE_WITH_COND 1
-#include "scene_body.inc"
-#undef SCENE_WITH_COND
-#undef SCENE_WITH_DRUDE
-#undef SCENE_WITH_MESH
-}
-
-// the arguments the entry points share (quantity one of qlo .. qhi), checked and turned into SceneArgs;
+// the entry point's arguments but the side and mesh tables, checked and turned into SceneArgs;
 // 0: launch, -1: nothing to do
-int scene_args(const void* tab, int nobj, int quantity, int qlo, int qhi, const int* points, int npts,
-               const int* origin, const int* shape, const int* stride, double mod, int cull, void* out, SceneArgs& A) {
-
+int scene_args(const void* tab, int nobj, int quantity, const int* points, int npts, const int* origin,
+               const int* shape, const int* stride, double mod, int cull, void* out, SceneArgs& A) {
   if (!tab || !points || !origin || !shape || !stride || !out) return (int)hipErrorInvalidValue;
-  if (nobj < 0 || nobj > SCENE_MAX_OBJECTS || quantity < qlo || quantity > qhi) return (int)hipErrorInvalidValue;
+  if (nobj < 0 || nobj > SCENE_MAX_OBJECTS || quantity < 0 || quantity >= SCENE_QUANTITIES)
+    return (int)hipErrorInvalidValue;
   if (npts != 1 && npts != 2 && npts != 4 && npts != 8) return (int)hipErrorInvalidValue;
   if (mod != 1.0 && mod != 2.0) return (int)hipErrorInvalidValue;
   A = SceneArgs{};
@@ -317,118 +494,49 @@ int scene_args(const void* tab, int nobj, int quantity, int qlo, int qhi, const 
   return 0;
 }
 
+// the launch of one (quantity, mesh): `side` and `M` go in where the variant reads them
+template <int Q, bool MESH>
+void scene_launch(const SceneEnt* tab, const void* side, double* out, const SceneArgs& A, const SceneMesh& M,
+                  hipStream_t s) {
+  SceneSide<Q> S{};
+  SceneMeshArg<MESH> G{};
+  if constexpr (q_reads_drude(Q) || q_reads_cond(Q)) S = (SceneSide<Q>)side;
+  if constexpr (MESH) G = M;
+  k_scene_sample<Q, MESH><<<cdiv(A.waves, 4), 256, 0, s>>>(tab, S, out, A, G);
+}
+constexpr decltype(&scene_launch<0, false>) SCENE_LAUNCH[SCENE_QUANTITIES][2] = {
+    {scene_launch<0, false>, scene_launch<0, true>}, {scene_launch<1, false>, scene_launch<1, true>},
+    {scene_launch<2, false>, scene_launch<2, true>}, {scene_launch<3, false>, scene_launch<3, true>},
+    {scene_launch<4, false>, scene_launch<4, true>}, {scene_launch<5, false>, scene_launch<5, true>}};
+
 }  // namespace
 
-// One component's averaged material of a file scene: `tab` = nobj device
-// entries of fdtd_scene_ent_size() bytes (at most fdtd_scene_max_objects()),
-// quantity 0 = eps / 1 = omega, `points` = npts x 3 eps-grid offsets (npts 1, 2,
-// 4 or 8), `origin`, `shape`, `stride` (1 or 2) of 3 ints each, `out` = the
-// shape's cells, contiguous fp64.  cull = 0 evaluates every object everywhere.
+// One component's averaged material of a file scene: `tab` = nobj device entries of fdtd_scene_ent_size()
+// bytes (at most fdtd_scene_max_objects()), quantity 0 = eps, 1 = omega, 2 = omega_m, 3 = gamma, 4 = gamma_m,
+// 5 = cond, `points` = npts x 3 eps-grid offsets (npts 1, 2, 4 or 8), `origin`, `shape`, `stride` (1 or 2) of
+// 3 ints each, `out` = the shape's cells, contiguous fp64.  cull = 0 evaluates every object everywhere.
+// `side` = the quantity's side table on the device, one row per object, `side_bytes` its size: none (null,
+// 0) for eps and omega, triples (gamma_e, omega_m, gamma_m) of fdtd_scene_drude_size() bytes, rad/s, for
+// quantities 2 to 4, doubles (S/m) for cond; a table of another size is refused.
+// `ranges` selects the mesh form (kind 3 entries, their bounding boxes in p / q): nobj device pairs (first,
+// count) of ints, a mesh's triangles among `tris` = ntris device triangles of fdtd_scene_tri_size() bytes (at
+// most fdtd_scene_max_triangles()), every triangle's vertices in ascending (x, y, z) order.  A range is
+// clamped to the buffer on the device; the caller checks it on the host.  Without `ranges`: no `tris`, ntris 0.
 FDTD_API int fdtd_scene_sample(const void* tab, int nobj, int quantity, const int* points, int npts,
                                const int* origin, const int* shape, const int* stride, double mod, int cull,
-                               void* out, void* s) {
+                               void* out, void* s, const void* side, size_t side_bytes, const void* tris, int ntris,
+                               const void* ranges) {
+  const bool mesh = ranges != nullptr;
+  if (mesh && (ntris < 0 || ntris > SCENE_MAX_TRIANGLES || (ntris > 0 && !tris))) return (int)hipErrorInvalidValue;
+  if (!mesh && (tris || ntris != 0)) return (int)hipErrorInvalidValue;
   SceneArgs A;
-  const int rc = scene_args(tab, nobj, quantity, 0, 1, points, npts, origin, shape, stride, mod, cull, out, A);
-  if (rc) return rc < 0 ? 0 : rc;
-  const unsigned blocks = cdiv(A.waves, 4);
-  if (quantity == 0)
-    k_scene_sample<0><<<blocks, 256, 0, (hipStream_t)s>>>((const SceneEnt*)tab, (double*)out, A);
-  else
-    k_scene_sample<1><<<blocks, 256, 0, (hipStream_t)s>>>((const SceneEnt*)tab, (double*)out, A);
-  FDTD_RETURN_LAUNCH_STATUS();
-}
-
-// The same for a scene with meshes (kind 3 entries, their bounding boxes in p / q): `tris` = ntris
-// device triangles of fdtd_scene_tri_size() bytes (at most fdtd_scene_max_triangles()), every triangle's
-// vertices in ascending (x, y, z) order; `ranges` = nobj device pairs (first, count) of ints, a mesh's
-// triangles.  A range is clamped to the buffer on the device; the caller checks it on the host.
-FDTD_API int fdtd_scene_sample_mesh(const void* tab, int nobj, int quantity, const int* points, int npts,
-                                    const int* origin, const int* shape, const int* stride, double mod, int cull,
-                                    void* out, void* s, const void* tris, int ntris, const void* ranges) {
-  if (ntris < 0 || ntris > SCENE_MAX_TRIANGLES || (ntris > 0 && !tris) || !ranges) return (int)hipErrorInvalidValue;
-  SceneArgs A;
-  const int rc = scene_args(tab, nobj, quantity, 0, 1, points, npts, origin, shape, stride, mod, cull, out, A);
-  if (rc) return rc < 0 ? 0 : rc;
+  const int rc = scene_args(tab, nobj, quantity, points, npts, origin, shape, stride, mod, cull, out, A);
+  if (rc > 0) return rc;
+  const size_t row = q_reads_drude(quantity) ? sizeof(SceneDrude) : q_reads_cond(quantity) ? sizeof(double) : 0;
+  if ((side != nullptr) != (row != 0) || side_bytes != (size_t)nobj * row) return (int)hipErrorInvalidValue;
+  if (rc < 0) return 0;
   const SceneMesh M = {(const SceneTri*)tris, (const SceneRange*)ranges, ntris};
-  const unsigned blocks = cdiv(A.waves, 4);
-  if (quantity == 0)
-    k_scene_sample_mesh<0><<<blocks, 256, 0, (hipStream_t)s>>>((const SceneEnt*)tab, (double*)out, A, M);
-  else
-    k_scene_sample_mesh<1><<<blocks, 256, 0, (hipStream_t)s>>>((const SceneEnt*)tab, (double*)out, A, M);
-  FDTD_RETURN_LAUNCH_STATUS();
-}
-
-// The magnetic plasma frequency and the collision frequencies: quantity 2 = omega_m, 3 = gamma, 4 =
-// gamma_m, `drude` = ndrude device triples (gamma_e, omega_m, gamma_m) of doubles, one per object
-// (ndrude == nobj); everything else as fdtd_scene_sample.
-FDTD_API int fdtd_scene_sample_drude(const void* tab, int nobj, int quantity, const int* points, int npts,
-                                     const int* origin, const int* shape, const int* stride, double mod, int cull,
-                                     void* out, void* s, const void* drude, int ndrude) {
-  if (!drude || ndrude != nobj) return (int)hipErrorInvalidValue;
-  SceneArgs A;
-  const int rc = scene_args(tab, nobj, quantity, 2, 4, points, npts, origin, shape, stride, mod, cull, out, A);
-  if (rc) return rc < 0 ? 0 : rc;
-  const unsigned blocks = cdiv(A.waves, 4);
-  const SceneEnt* T = (const SceneEnt*)tab;
-  const SceneDrude* D = (const SceneDrude*)drude;
-  if (quantity == 2)
-    k_scene_sample_drude<2><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A);
-  else if (quantity == 3)
-    k_scene_sample_drude<3><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A);
-  else
-    k_scene_sample_drude<4><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A);
-  FDTD_RETURN_LAUNCH_STATUS();
-}
-
-// The same for a scene with meshes: `tris`, `ntris`, `ranges` as fdtd_scene_sample_mesh.
-FDTD_API int fdtd_scene_sample_drude_mesh(const void* tab, int nobj, int quantity, const int* points, int npts,
-                                          const int* origin, const int* shape, const int* stride, double mod,
-                                          int cull, void* out, void* s, const void* drude, int ndrude,
-                                          const void* tris, int ntris, const void* ranges) {
-  if (!drude || ndrude != nobj) return (int)hipErrorInvalidValue;
-  if (ntris < 0 || ntris > SCENE_MAX_TRIANGLES || (ntris > 0 && !tris) || !ranges) return (int)hipErrorInvalidValue;
-  SceneArgs A;
-  const int rc = scene_args(tab, nobj, quantity, 2, 4, points, npts, origin, shape, stride, mod, cull, out, A);
-  if (rc) return rc < 0 ? 0 : rc;
-  const SceneMesh M = {(const SceneTri*)tris, (const SceneRange*)ranges, ntris};
-  const unsigned blocks = cdiv(A.waves, 4);
-  const SceneEnt* T = (const SceneEnt*)tab;
-  const SceneDrude* D = (const SceneDrude*)drude;
-  if (quantity == 2)
-    k_scene_sample_drude_mesh<2><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A, M);
-  else if (quantity == 3)
-    k_scene_sample_drude_mesh<3><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A, M);
-  else
-    k_scene_sample_drude_mesh<4><<<blocks, 256, 0, (hipStream_t)s>>>(T, D, (double*)out, A, M);
-  FDTD_RETURN_LAUNCH_STATUS();
-}
-// The conductivity: quantity 5, `cond` = ncond device doubles, one per object (ncond == nobj, S/m);
-// everything else as fdtd_scene_sample.
-FDTD_API int fdtd_scene_sample_cond(const void* tab, int nobj, int quantity, const int* points, int npts,
-                                    const int* origin, const int* shape, const int* stride, double mod, int cull,
-                                    void* out, void* s, const void* cond, int ncond) {
-  if (!cond || ncond != nobj) return (int)hipErrorInvalidValue;
-  SceneArgs A;
-  const int rc = scene_args(tab, nobj, quantity, 5, 5, points, npts, origin, shape, stride, mod, cull, out, A);
-  if (rc) return rc < 0 ? 0 : rc;
-  k_scene_sample_cond<5><<<cdiv(A.waves, 4), 256, 0, (hipStream_t)s>>>((const SceneEnt*)tab, (const double*)cond,
-                                                                       (double*)out, A);
-  FDTD_RETURN_LAUNCH_STATUS();
-}
-
-// The same for a scene with meshes: `tris`, `ntris`, `ranges` as fdtd_scene_sample_mesh.
-FDTD_API int fdtd_scene_sample_cond_mesh(const void* tab, int nobj, int quantity, const int* points, int npts,
-                                         const int* origin, const int* shape, const int* stride, double mod,
-                                         int cull, void* out, void* s, const void* cond, int ncond,
-                                         const void* tris, int ntris, const void* ranges) {
-  if (!cond || ncond != nobj) return (int)hipErrorInvalidValue;
-  if (ntris < 0 || ntris > SCENE_MAX_TRIANGLES || (ntris > 0 && !tris) || !ranges) return (int)hipErrorInvalidValue;
-  SceneArgs A;
-  const int rc = scene_args(tab, nobj, quantity, 5, 5, points, npts, origin, shape, stride, mod, cull, out, A);
-  if (rc) return rc < 0 ? 0 : rc;
-  const SceneMesh M = {(const SceneTri*)tris, (const SceneRange*)ranges, ntris};
-  k_scene_sample_cond_mesh<5><<<cdiv(A.waves, 4), 256, 0, (hipStream_t)s>>>((const SceneEnt*)tab,
-                                                                            (const double*)cond, (double*)out, A, M);
+  SCENE_LAUNCH[quantity][mesh]((const SceneEnt*)tab, side, (double*)out, A, M, (hipStream_t)s);
   FDTD_RETURN_LAUNCH_STATUS();
 }
 FDTD_API int fdtd_scene_drude_size() { return (int)sizeof(SceneDrude); }
@@ -436,3 +544,4 @@ FDTD_API int fdtd_scene_ent_size() { return (int)sizeof(SceneEnt); }
 FDTD_API int fdtd_scene_max_objects() { return (int)SCENE_MAX_OBJECTS; }
 FDTD_API int fdtd_scene_tri_size() { return (int)sizeof(SceneTri); }
 FDTD_API int fdtd_scene_max_triangles() { return (int)SCENE_MAX_TRIANGLES; }
+

@@ -20,72 +20,55 @@ from .hip_lib import HipError, _check, _ptr, _stream, c_double, c_int
 class HipSceneOps:
     """Needs ``lib``, ``device`` and ``launches`` of :class:`~.hip_ops.HipOps`."""
 
+    def _scene_dev(self, table: SceneTable, suffix: str, build):
+        """One of ``table``'s tables on the device: ``build()`` = (a tuple of)
+        numpy arrays, a row per entry, each padded to at least one row (so a
+        pointer is never null); cached on ``table`` per device and ``suffix``."""
+        key = str(torch.device(self.device)) + suffix
+        dev = table.device_tables.get(key)
+        if dev is None:
+            def padded(rows):
+                rows = torch.from_numpy(rows.copy())
+                host = rows.new_zeros((max(1, len(rows)),) + tuple(rows.shape[1:]))
+                host[:len(rows)] = rows
+                return host.to(self.device)
+            host = build()
+            dev = table.device_tables[key] = (tuple(map(padded, host)) if isinstance(host, tuple) else padded(host))
+        return dev
+
     def _scene_table(self, table: SceneTable) -> torch.Tensor:
-        """The table on the device (at least one entry, so never a null
-        pointer), cached on ``table`` per device."""
+        """The entries, SCENE_ENT_SIZE bytes each."""
         raw = self.lib.raw
         if int(raw.fdtd_scene_ent_size()) != SCENE_ENT_SIZE or int(raw.fdtd_scene_max_objects()) != SCENE_MAX_OBJECTS:
             raise HipError("SceneEnt layout mismatch")
-        key = str(torch.device(self.device))
-        dev = table.device_tables.get(key)
-        if dev is None:
-            host = torch.zeros((max(1, len(table)), SCENE_ENT_SIZE), dtype=torch.uint8)
-            if len(table):
-                host[:len(table)] = torch.from_numpy(table.ents.view("u1").reshape(len(table), SCENE_ENT_SIZE).copy())
-            dev = table.device_tables[key] = host.to(self.device)
-        return dev
+        return self._scene_dev(table, "", lambda: table.ents.view("u1").reshape(len(table), SCENE_ENT_SIZE))
 
     def _scene_triangles(self, table: SceneTable):
-        """(triangles, ranges) of a table with meshes on the device: 72 bytes
-        a triangle (at least one, so never a null pointer), two ints an
-        object; cached on ``table`` per device."""
+        """(triangles, ranges) of a table with meshes: 72 bytes a triangle, two
+        ints an object."""
         raw = self.lib.raw
         if int(raw.fdtd_scene_tri_size()) != 72 or int(raw.fdtd_scene_max_triangles()) != SCENE_MAX_TRIANGLES:
             raise HipError("SceneTri layout mismatch")
-        key = str(torch.device(self.device)) + " triangles"
-        dev = table.device_tables.get(key)
-        if dev is None:
-            tris = torch.zeros((max(1, len(table.tris)), 9), dtype=torch.float64)
-            tris[:len(table.tris)] = torch.from_numpy(table.tris.reshape(-1, 9).copy())
-            ranges = torch.zeros((max(1, len(table)), 2), dtype=torch.int32)
-            ranges[:len(table)] = torch.from_numpy(table.ranges.copy())
-            dev = table.device_tables[key] = (tris.to(self.device), ranges.to(self.device))
-        return dev
+        return self._scene_dev(table, " triangles", lambda: (table.tris.reshape(-1, 9), table.ranges))
 
     def _scene_drude(self, table: SceneTable) -> torch.Tensor:
-        """``table.drude`` on the device: (gamma_e, omega_m, gamma_m) an object,
-        24 bytes (at least one row, so never a null pointer); cached on
-        ``table`` per device."""
+        """``table.drude``: (gamma_e, omega_m, gamma_m) an object, 24 bytes."""
         if int(self.lib.raw.fdtd_scene_drude_size()) != 24:
             raise HipError("SceneDrude layout mismatch")
-        key = str(torch.device(self.device)) + " drude"
-        dev = table.device_tables.get(key)
-        if dev is None:
-            host = torch.zeros((max(1, len(table)), 3), dtype=torch.float64)
-            host[:len(table)] = torch.from_numpy(table.drude.copy())
-            dev = table.device_tables[key] = host.to(self.device)
-        return dev
+        return self._scene_dev(table, " drude", lambda: table.drude)
 
     def _scene_cond(self, table: SceneTable) -> torch.Tensor:
-        """``table.cond`` on the device: a double an object (at least one, so
-        never a null pointer); cached on ``table`` per device."""
-        key = str(torch.device(self.device)) + " cond"
-        dev = table.device_tables.get(key)
-        if dev is None:
-            host = torch.zeros((max(1, len(table)),), dtype=torch.float64)
-            host[:len(table)] = torch.from_numpy(table.cond.copy())
-            dev = table.device_tables[key] = host.to(self.device)
-        return dev
+        """``table.cond``: a double an object."""
+        return self._scene_dev(table, " cond", lambda: table.cond)
 
     def scene_sample(self, table, quantity: str, points, origin, shape, stride, mod, out=None,
                      cull: bool = True) -> torch.Tensor:
         """The contract of ``TorchOps.scene_sample`` in ONE launch of
-        k_scene_sample (k_scene_sample_mesh when the table holds a mesh;
-        k_scene_sample_drude and its mesh twin for omega_m, gamma and gamma_m,
-        which read ``table.drude`` too; k_scene_sample_cond and its mesh twin
-        for cond, which read ``table.cond``).  ``out``: a contiguous fp64 device
-        tensor of ``shape`` to fill (allocated otherwise); ``cull`` = False
-        evaluates every object at every cell (measurements)."""
+        k_scene_sample<Q, MESH> (MESH when the table holds a mesh; omega_m,
+        gamma and gamma_m read ``table.drude`` as their side table, cond
+        ``table.cond``).  ``out``: a contiguous fp64 device tensor of ``shape``
+        to fill (allocated otherwise); ``cull`` = False evaluates every object
+        at every cell (measurements)."""
         if not isinstance(table, SceneTable):
             raise HipError("scene_sample: a SceneTable, got %r" % type(table).__name__)
         if len(table) > SCENE_MAX_OBJECTS:
@@ -118,22 +101,16 @@ class HipSceneOps:
         tab = self._scene_table(table)
         i3 = ctypes.c_int * 3
         flat = [v for p in pts for v in p]
-        args = (_ptr(tab), c_int(len(table)), c_int(q), (ctypes.c_int * len(flat))(*flat), c_int(len(pts)),
-                i3(*origin), i3(*shape), i3(*stride), c_double(mod), c_int(1 if cull else 0), _ptr(out), _stream())
-        raw = self.lib.raw
-        if q == 5:   # cond: the conductivities
-            args += (_ptr(self._scene_cond(table)), c_int(len(table.cond)))
-        elif q >= 2:   # omega_m, gamma, gamma_m: the second table
-            args += (_ptr(self._scene_drude(table)), c_int(len(drude)))
-        name = "fdtd_scene_sample" + ("_cond" if q == 5 else "_drude" if q >= 2 else "")
-        if meshes:
-            tris, ranges = self._scene_triangles(table)
-            f = getattr(raw, name + "_mesh")
-            args += (_ptr(tris), c_int(len(table.tris)), _ptr(ranges))
-        else:
-            f = getattr(raw, name)
+        # the quantity's side table and its true size: the conductivities, the second table or none
+        side, side_bytes = ((self._scene_cond(table), table.cond.nbytes) if q == 5 else
+                            (self._scene_drude(table), drude.nbytes) if q >= 2 else (None, 0))
+        tris, ranges = self._scene_triangles(table) if meshes else (None, None)
+        f = self.lib.raw.fdtd_scene_sample
         f.restype = c_int
-        rc = f(*args)
+        rc = f(_ptr(tab), c_int(len(table)), c_int(q), (ctypes.c_int * len(flat))(*flat), c_int(len(pts)),
+               i3(*origin), i3(*shape), i3(*stride), c_double(mod), c_int(1 if cull else 0), _ptr(out), _stream(),
+               _ptr(side), ctypes.c_size_t(side_bytes), _ptr(tris), c_int(len(table.tris) if meshes else 0),
+               _ptr(ranges))
         _check(rc, "scene_sample")
         self.launches += 1
         return out

@@ -7,6 +7,8 @@ plain window on three shell streams.  Format, physics and plan tests:
 test_lossy_cpu.py.
 """
 
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -194,8 +196,27 @@ def test_cond_table_checks(gpu):
             hip.scene_sample(tab, "cond", [(0, 0, 0)], origin, shape, (1, 1, 1), 1.0, out=out)
     with pytest.raises(HipError):
         hip.scene_sample(good, "sigma", [(0, 0, 0)], origin, shape, (1, 1, 1), 1.0, out=out)
+    # the entry point itself: no conductivities, a row short or a row long, the Drude table with its true size
+    f = hip.lib.raw.fdtd_scene_sample
+    f.restype = ctypes.c_int
+    i3, vp = ctypes.c_int * 3, ctypes.c_void_p
+    dev_tab, dev_cond, dev_drude = hip._scene_table(good), hip._scene_cond(good), hip._scene_drude(good)
+    assert dev_cond.numel() == len(good)
+
+    def entry(side=dev_cond, side_bytes=8 * len(good)):
+        return f(vp(dev_tab.data_ptr()), ctypes.c_int(len(good)), ctypes.c_int(5), i3(0, 0, 0), ctypes.c_int(1),
+                 i3(*origin), i3(*shape), i3(1, 1, 1), ctypes.c_double(1.0), ctypes.c_int(1), vp(out.data_ptr()),
+                 vp(torch.cuda.current_stream().cuda_stream), vp(None if side is None else side.data_ptr()),
+                 ctypes.c_size_t(side_bytes), vp(None), ctypes.c_int(0), vp(None))
+
+    for kw in (dict(side=None), dict(side=None, side_bytes=0), dict(side_bytes=8 * (len(good) - 1)),
+               dict(side_bytes=8 * (len(good) + 1)), dict(side=dev_drude, side_bytes=24 * len(good))):
+        assert entry(**kw) == 1, kw   # hipErrorInvalidValue
     torch.cuda.synchronize()
     assert hip.launches == n0 and bool((out == SENTINEL).all())
+    assert entry() == 0
+    torch.cuda.synchronize()
+    assert not bool((out == SENTINEL).any())
 
 
 # ------------------------------------------------------------------ whole runs

@@ -1,4 +1,4 @@
-"""Triangle meshes in file scenes on the device: k_scene_sample_mesh
+"""Triangle meshes in file scenes on the device: k_scene_sample<Q, true>
 (csrc/scene_kernels.hip) against the torch op evaluated on the CPU, what it
 leaves untouched, its refusals, and a run end to end from a binary STL."""
 
@@ -151,7 +151,7 @@ def test_refusals_launch_nothing(hip, gpu):
     many.tris = np.broadcast_to(many.tris[:1], (SCENE_MAX_TRIANGLES + 1, 3, 3))   # (a view: nothing that size exists)
     refused(many, "a scene holds")
 
-    f = hip.lib.raw.fdtd_scene_sample_mesh
+    f = hip.lib.raw.fdtd_scene_sample
     f.restype = ctypes.c_int
     i3 = ctypes.c_int * 3
     dev_tab = hip._scene_table(tab)
@@ -162,8 +162,10 @@ def test_refusals_launch_nothing(hip, gpu):
         vp = ctypes.c_void_p
         return f(vp(dev_tab.data_ptr()), ctypes.c_int(len(tab)), ctypes.c_int(0), i3(0, 0, 0), ctypes.c_int(1),
                  i3(*origin), i3(*shape), i3(1, 1, 1), ctypes.c_double(1.0), ctypes.c_int(1), vp(out_p),
-                 vp(torch.cuda.current_stream().cuda_stream), vp(tris_p), ctypes.c_int(ntris), vp(ranges_p))
+                 vp(torch.cuda.current_stream().cuda_stream), vp(None), ctypes.c_size_t(0), vp(tris_p),
+                 ctypes.c_int(ntris), vp(ranges_p))
 
+    # (without ranges this is the plain form, which takes no triangles)
     for kw in (dict(tris_p=None), dict(ranges_p=None), dict(ntris=-1), dict(ntris=SCENE_MAX_TRIANGLES + 1),
                dict(out_p=None)):
         assert entry(**kw) == 1, kw   # hipErrorInvalidValue

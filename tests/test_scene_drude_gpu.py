@@ -1,6 +1,6 @@
 """Damped and magnetic Drude media of file scenes on the device:
-k_scene_sample_drude and its mesh twin (csrc/scene_kernels.hip) against the
-torch op evaluated on the CPU, their refusals, and runs end to end."""
+k_scene_sample<Q, MESH> for Q = omega_m, gamma, gamma_m (csrc/scene_kernels.hip)
+against the torch op evaluated on the CPU, its refusals, and runs end to end."""
 
 import ctypes
 import dataclasses
@@ -120,7 +120,7 @@ def test_kernel_equals_oracle_2d(hip, oracle):
 @pytest.mark.parametrize("shape,origin", REGIONS, ids=["9x7x11", "5x3x130"])
 def test_mesh_twin_equals_oracle(hip, oracle, shape, origin):
     """The same with a small closed mesh painted between the primitives
-    (k_scene_sample_drude_mesh)."""
+    (the MESH instantiations)."""
     objs = straddling(origin, shape, mesh=True)
     for smoothing in ("linear", "none"):
         tab = build_table(objs, "3d", smoothing, FREQ)
@@ -133,6 +133,35 @@ def test_mesh_twin_equals_oracle(hip, oracle, shape, origin):
     tab = build_table(objs, "3d", "linear", FREQ)
     args = (stencil("Hx", 1), origin, shape, (1, 1, 1), 1.0)
     assert not torch.equal(hip.scene_sample(tab, "gamma", *args), hip.scene_sample(bare, "gamma", *args))
+
+
+@pytest.mark.parametrize("shape,origin", REGIONS, ids=["9x7x11", "5x3x130"])
+def test_dispatch_of_every_quantity_and_form(hip, oracle, shape, origin):
+    """The one entry point's table of launches: each of the six quantities
+    without and with a mesh, on a region of odd z (scalar stores) and one of
+    two z tiles (vector stores), equal to the torch op bit for bit; the mesh
+    changes every quantity, so its instantiation is the one that ran."""
+    lo = [float(o) for o in origin]
+    mid = [o + s / 2 + 0.13 for o, s in zip(lo, shape)]
+    # (a lossy sphere under the others: sigma and omega_p exclude each other on an object)
+    lossy = {"shape": "sphere", "center": mid, "radius": 3.1, "eps": 1.2, "sigma": 0.8}
+    pts = stencil("Hx", 1)
+    assert len(pts) == 4
+    got = {}
+    for mesh in (False, True):
+        objs = [lossy] + straddling(origin, shape, mesh=mesh)
+        objs[4] = dict(objs[4], sigma=2.5)
+        tab = build_table(objs, "3d", "linear", FREQ)
+        assert tab.has_meshes() == mesh
+        for q in ("eps", "omega") + NEW + ("cond",):
+            want = oracle.scene_sample(tab, q, pts, origin, shape, (1, 1, 1), 1.0)
+            n0 = hip.launches
+            got[q, mesh] = hip.scene_sample(tab, q, pts, origin, shape, (1, 1, 1), 1.0)
+            assert hip.launches == n0 + 1
+            assert torch.equal(got[q, mesh].cpu(), want), (q, mesh, int((got[q, mesh].cpu() != want).sum()))
+            assert len(torch.unique(want)) >= 3, ("trivial scene", q, mesh)
+    for q in ("eps", "omega") + NEW + ("cond",):
+        assert not torch.equal(got[q, True], got[q, False]), (q, "the mesh changed nothing")
 
 
 @pytest.mark.parametrize("shape", [(5, 3, 130), (9, 7, 11), (6, 70, 1)], ids=["even-z", "odd-z", "one-z"])
@@ -182,23 +211,21 @@ def test_refusals_launch_nothing(hip, gpu):
     refused(out=out[:3])
     refused(shape=(4, 3, 7), out=out)
     refused(out=torch.full(shape, SENTINEL, dtype=torch.float64))  # not on the device
-    # the entry points themselves
+    # the entry point itself: the Drude table (its true size) with a quantity of another group, a table that
+    # is missing, a row short or a row long, and the shared checks
     i3 = ctypes.c_int * 3
     vp = ctypes.c_void_p
     dev_tab, dev_drude = hip._scene_table(tab), hip._scene_drude(tab)
     assert dev_drude.numel() == 3 * len(tab)
     stream = torch.cuda.current_stream().cuda_stream
+    f = hip.lib.raw.fdtd_scene_sample
+    f.restype = ctypes.c_int
 
     def entry(quantity=3, tab_p=dev_tab.data_ptr(), nobj=len(tab), drude_p=dev_drude.data_ptr(), ndrude=len(tab),
-              out_p=out.data_ptr(), shp=i3(*shape), mesh=False, ranges_p=dev_tab.data_ptr()):
-        f = hip.lib.raw.fdtd_scene_sample_drude_mesh if mesh else hip.lib.raw.fdtd_scene_sample_drude
-        f.restype = ctypes.c_int
-        args = (vp(tab_p), ctypes.c_int(nobj), ctypes.c_int(quantity), i3(0, 0, 0), ctypes.c_int(1), i3(0, 0, 0), shp,
-                i3(1, 1, 1), ctypes.c_double(1.0), ctypes.c_int(1), vp(out_p), vp(stream), vp(drude_p),
-                ctypes.c_int(ndrude))
-        if mesh:
-            args += (vp(None), ctypes.c_int(0), vp(ranges_p))
-        return f(*args)
+              out_p=out.data_ptr(), shp=i3(*shape), mesh=False, ranges_p=dev_tab.data_ptr(), tris_p=None):
+        return f(vp(tab_p), ctypes.c_int(nobj), ctypes.c_int(quantity), i3(0, 0, 0), ctypes.c_int(1), i3(0, 0, 0), shp,
+                 i3(1, 1, 1), ctypes.c_double(1.0), ctypes.c_int(1), vp(out_p), vp(stream), vp(drude_p),
+                 ctypes.c_size_t(24 * ndrude), vp(tris_p), ctypes.c_int(0), vp(ranges_p if mesh else None))
 
     for mesh in (False, True):
         for kw in (dict(quantity=0), dict(quantity=1), dict(quantity=5), dict(quantity=-1), dict(tab_p=None),
@@ -206,7 +233,7 @@ def test_refusals_launch_nothing(hip, gpu):
                    dict(nobj=-1, ndrude=-1), dict(shp=i3(4, -3, 6))):
             assert entry(mesh=mesh, **kw) == 1, (mesh, kw)   # hipErrorInvalidValue
         assert entry(mesh=mesh, shp=i3(4, 0, 6)) == 0   # an empty region: nothing launched, no error
-    assert entry(mesh=True, ranges_p=None) == 1
+    assert entry(mesh=True, ranges_p=None, tris_p=dev_tab.data_ptr()) == 1   # triangles without ranges
     torch.cuda.synchronize()
     assert bool((out == SENTINEL).all())
     assert entry() == 0

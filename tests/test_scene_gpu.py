@@ -158,14 +158,18 @@ def test_refusals_launch_nothing(hip, gpu):
     assert dev_tab.numel() == len(tab) * SCENE_ENT_SIZE
 
     def entry(tab_p=dev_tab.data_ptr(), nobj=len(tab), pts=i3(0, 0, 0), npts=1, org=i3(0, 0, 0), shp=i3(*shape),
-              std=i3(1, 1, 1), out_p=out.data_ptr()):
+              std=i3(1, 1, 1), out_p=out.data_ptr(), q=0, side_p=None, side_bytes=0, tris_p=None, ntris=0):
         vp = ctypes.c_void_p
-        return f(vp(tab_p), ctypes.c_int(nobj), ctypes.c_int(0), pts, ctypes.c_int(npts), org, shp, std,
-                 ctypes.c_double(1.0), ctypes.c_int(1), vp(out_p), vp(torch.cuda.current_stream().cuda_stream))
+        return f(vp(tab_p), ctypes.c_int(nobj), ctypes.c_int(q), pts, ctypes.c_int(npts), org, shp, std,
+                 ctypes.c_double(1.0), ctypes.c_int(1), vp(out_p), vp(torch.cuda.current_stream().cuda_stream),
+                 vp(side_p), ctypes.c_size_t(side_bytes), vp(tris_p), ctypes.c_int(ntris), vp(None))
 
+    # (and what eps and omega have none of: a side table or its size, triangles without ranges)
     for kw in (dict(tab_p=None), dict(out_p=None), dict(pts=None), dict(org=None), dict(shp=None), dict(std=None),
                dict(shp=i3(4, -3, 6)), dict(npts=0), dict(npts=9), dict(npts=3), dict(nobj=-1),
-               dict(nobj=SCENE_MAX_OBJECTS + 1), dict(std=i3(1, 0, 1))):
+               dict(nobj=SCENE_MAX_OBJECTS + 1), dict(std=i3(1, 0, 1)), dict(q=-1), dict(q=6),
+               dict(side_p=dev_tab.data_ptr()), dict(side_bytes=8), dict(q=1, side_p=dev_tab.data_ptr(), side_bytes=8),
+               dict(tris_p=dev_tab.data_ptr()), dict(ntris=1)):
         assert entry(**kw) == 1, kw   # hipErrorInvalidValue
     assert entry(shp=i3(4, 0, 6)) == 0   # an empty region: nothing launched, no error
     torch.cuda.synchronize()
