@@ -4,7 +4,6 @@ validation, and monitors end to end -- the decay-based early stop on stepped
 and hybrid passes, blocked vacuum passes, 2D and 1D -- against the fp64 CPU
 oracle (models/energy.py)."""
 import dataclasses
-import threading
 
 import pytest
 import torch
@@ -14,9 +13,7 @@ from fdtd3d_amd.models.energy import energy_from_config
 from fdtd3d_amd.models.scheme import SchemeConfig, YeeScheme
 from fdtd3d_amd.ops import make_ops
 from fdtd3d_amd.ops.energy import EnergyEntries
-from fdtd3d_amd.parallel.comm import LocalHub
-from fdtd3d_amd.parallel.halo import HaloExchanger
-from fdtd3d_amd.parallel.topology import ParallelGridCore
+from rank_threads import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -238,39 +235,18 @@ def test_series_end_to_end(gpu, name, dtype):
 
 # ---------------------------------------------------------- GPU thread ranks
 def _run_ranks(cfg, world, axes, buf, device):
-    """The monitor on decomposed HIP ranks: one thread and one stream per
-    rank over the in-process transport (the scheme of
-    tests/test_parallel_gpu.py).  Per rank: (t, stopped_at, series)."""
-    core = ParallelGridCore.create(cfg.size, world, axes, active_axes=(0, 1, 2))
-    hub = LocalHub(world)
-    dt = torch.float32 if cfg.dtype == "f32" else torch.float64
-    out, errors = [None] * world, []
+    """The monitor on decomposed HIP ranks (tests/rank_threads.py: one thread
+    and one stream per rank over the in-process transport).  Per rank: (t,
+    stopped_at, series)."""
+    topo = tuple(world if a == axes else 1 for a in "xyz")
 
-    def body(rank):
-        try:
-            with torch.cuda.stream(torch.cuda.Stream(device=device)):
-                dom = core.domain(rank, buf, align_z=4 if cfg.time_block > 1 else 1, align_axis=2)
-                halo = HaloExchanger(dom, comm=hub.comm(rank))
-                s = YeeScheme(cfg, make_ops("hip", None, device, dt), dom, halo)
-                s.init_scheme()
-                s.init_grids()
-                assert s.tb == max(1, cfg.time_block)
-                mon = energy_from_config(s)
-                s.perform_steps()
-                halo.drain(s)
-                out[rank] = (s.t, mon.stopped_at, mon.series())
-            torch.cuda.synchronize()
-        except BaseException as e:  # surface thread failures in the test
-            errors.append(e)
+    def setup(s):
+        assert s.tb == max(1, cfg.time_block)
+        return energy_from_config(s)
 
-    ths = [threading.Thread(target=body, args=(r,)) for r in range(world)]
-    for t in ths:
-        t.start()
-    for t in ths:
-        t.join(timeout=600)
-    if errors:
-        raise errors[0]
-    return out
+    return run_ranks(cfg, topo, buf, "hip", device, setup=setup,
+                     collect=lambda s, mon: (s.t, mon.stopped_at, mon.series()),
+                     align_z=4 if cfg.time_block > 1 else 1, timeout=600)
 
 
 # 2 x 1 x 1 ranks: the early-stop scene on single split steps with face exchanges (every sample read, all-reduced,

@@ -236,42 +236,15 @@ SEAM_CFG = dict(size=(16, 16, 12), time_steps=10)
 def test_decomposed_equals_serial(gpu):
     """2 x 2 x 1 thread ranks on one GPU, 3-deep ghosts: entries on the rank
     seams, inside ghost zones and on an H component."""
-    import threading
-
-    from fdtd3d_amd.parallel.comm import LocalHub
-    from fdtd3d_amd.parallel.halo import HaloExchanger
-    from fdtd3d_amd.parallel.topology import ParallelGridCore
+    from rank_threads import run_ranks
     cfg = SchemeConfig(scheme="3d", scene="vacuum", dtype="f64", sources=SEAM, **SEAM_CFG)
     ser = fields(run(cfg, "hip", gpu))
-    world = 4
-    core = ParallelGridCore.create(cfg.size, world, "xy", (2, 2, 1), optimal=False, active_axes=(0, 1, 2))
-    hub = LocalHub(world)
-    schemes, errors = [None] * world, []
 
-    def body(rank):
-        try:
-            with torch.cuda.stream(torch.cuda.Stream(device=gpu)):
-                dom = core.domain(rank, 3, align_z=1, align_axis=2)
-                halo = HaloExchanger(dom, comm=hub.comm(rank))
-                s = YeeScheme(cfg, make_ops("hip", None, gpu, torch.float64), dom, halo)
-                s.init_scheme()
-                s.init_grids()
-                assert s.hybrid is None and s.tb == 1
-                s.perform_steps()
-                halo.drain(s)
-            torch.cuda.synchronize()
-            schemes[rank] = s
-        except BaseException as e:
-            errors.append(e)
+    def setup(s):
+        assert s.hybrid is None and s.tb == 1
 
-    ths = [threading.Thread(target=body, args=(r,)) for r in range(world)]
-    for t in ths:
-        t.start()
-    for t in ths:
-        t.join(timeout=120)
-    if errors:
-        raise errors[0]
-    assert tuple(core.topology) == (2, 2, 1)
+    schemes = run_ranks(cfg, (2, 2, 1), 3, "hip", gpu, setup=setup)
+    assert tuple(schemes[0].domain.topology) == (2, 2, 1)
     assert float(ser["Hx"].abs().max()) > 0
     for c in ser:
         full = torch.zeros(cfg.size, dtype=torch.float64)
